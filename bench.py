@@ -12,9 +12,14 @@ Headline (BASELINE.json `metric`): LDDMM step voxels/sec, 3D 128^3 -- one "step"
 benchmark is one `lddmm.expmap` call (10 Euler steps of the integrated EPDiff equation,
 BASELINE configs[3]) over a GLOBAL batch of 32 momentum fields of 3x128^3 fp32, sharded 32/N per
 GPU ("strong" scaling: the global batch is fixed), inputs resident in HBM, no data-path collective.
-value = (voxels * Euler steps) processed by all ranks / wall time (max over ranks).
+value = (voxels * Euler steps) processed by all ranks / wall time (max over ranks); ms_per_step = wall time of one
+timed step.
 
-Also on the same JSON line:
+A plain run does only that: set-up, --warmup W untimed steps, --steps K timed steps (per-entry-point HIP-event sums of
+the timed region in `breakdown_ms_per_step`), the result line.  --dump-outputs DIR also writes what the last timed step
+returned (`dump_outputs`); the inputs are seeded, so the same arguments give the same inputs on every run.
+
+With --full, also on the same JSON line (the --no-* options leave parts out):
   atlas_step    -- BASELINE configs[4], at every N: `LDDMMAtlasBuilder.iteration` (lddmm_step = 5-step expmap
                    -> interp -> loss -> backward through every operator -> momentum update, then ONE RCCL
                    all-reduce of the atlas gradient and the image update) on 160^3 subjects, global
@@ -725,6 +730,28 @@ def ensure_built(local_rank):
     time.sleep(2.0)  # let the linker finish writing
 
 
+DUMP_ITEM_MAX_BYTES = 32 << 20   # the first batch item is written whole up to this size (3 x 128^3 fp32: 25 MB)
+DUMP_SAMPLE = 1 << 21            # values of the seeded sample over the whole output (8 MB of float32)
+
+
+def dump_outputs(out_dir, h):
+    """--dump-outputs: what the last timed step returned to its caller -- this rank's lddmm.expmap result h, float32 --
+    as .npy files, 33 MB at the default sizes and never more than 40 MB:
+      expmap_h_item0.npy   h[0] in full (omitted when it is larger than DUMP_ITEM_MAX_BYTES);
+      expmap_h_sample.npy  h.flatten() at DUMP_SAMPLE flat indices drawn, sorted, from a CPU generator seeded with 0,
+                           so that the same arguments give the same indices on every run and every build."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    h = h.detach()
+    if h[0].numel() * h.element_size() <= DUMP_ITEM_MAX_BYTES:
+        np.save(os.path.join(out_dir, "expmap_h_item0.npy"), h[0].float().cpu().numpy())
+    flat = h.reshape(-1)
+    g = torch.Generator().manual_seed(0)
+    idx = torch.randint(0, flat.numel(), (min(DUMP_SAMPLE, flat.numel()),), generator=g).sort().values
+    np.save(os.path.join(out_dir, "expmap_h_sample.npy"), flat[idx.to(flat.device)].float().cpu().numpy())
+
+
 def parse_args():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -752,7 +779,17 @@ def parse_args():
     ap.add_argument("--no-epoch", action="store_true", help="skip the atlas_epoch leg")
     ap.add_argument("--cpu-sample-batch", type=int, default=16,
                     help="volumes in the all-cores CPU baseline sample (the one-thread sample is a quarter of it)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: the single-stream (roofline) and general-kernel passes, the atlas "
+                         "legs over a world-size-1 RCCL group, the micro-benchmarks and the CPU baseline.  The --no-* and "
+                         "--atlas-* options select among these")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned (rank 0's expmap result) as "
+                         "DIR/<name>.npy, float32, at most 64 MB")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 # LAGO_BENCH_SHARE_GPU=1: run the N-rank code path on ONE GPU (ranks share device 0, gloo instead of RCCL) -- for
@@ -861,7 +898,7 @@ def main():
     if args.batch % world:
         raise SystemExit(f"bench.py: --batch {args.batch} is not divisible by {world} ranks")
     force_dist, force_dist_detail = False, None
-    if world == 1 and FORCE_DIST and not (args.no_atlas and args.no_epoch):
+    if world == 1 and FORCE_DIST and args.full and not (args.no_atlas and args.no_epoch):
         force_dist, force_dist_detail = rccl_world1_probe()   # (a child process; nothing here has touched the GPU yet)
     if not torch.cuda.is_available():
         raise SystemExit("bench.py needs a GPU: the HIP path has no CPU fallback")
@@ -926,40 +963,44 @@ def main():
             kt.enabled = False
             ksum_timed = kt.summary()
         hmax = h.abs().max().item()
-        # ROOFLINE PASS (same process, same inputs, right after the timed region): the same shoots on
-        # ONE stream, so that a launch's HIP-event duration is the time the kernel needs by itself.  `roofline` and
-        # `single_stream` below come from here; the headline does not.
-        _lddmm.EXPMAP_STREAMS = 1
-        try:
-            with KernelTimer(ext, names) as kt1:
-                step()
-                torch.cuda.synchronize()
-                kt1.enabled = True
-                ts0 = time.perf_counter()
-                for _ in range(args.steps):
-                    h1 = step()
-                torch.cuda.synchronize()
-                t_single = (time.perf_counter() - ts0) / args.steps
-                kt1.enabled = False
-                ksum = kt1.summary()
-            single_bits = bool(torch.equal(h1, h))
-            del h1
-            # for comparison, untimed: the same single-stream shoot with every Euler step through the general kernels
-            # (an explicit zero phiinv switches off the closed-form first step; same result bit for bit)
-            t_general, same_bits = None, None
-            if not args.no_extras:
-                z = torch.zeros_like(m)
-                lm.expmap(metric, m, num_steps=E, phiinv=z)
-                torch.cuda.synchronize()
-                tg0 = time.perf_counter()
-                for _ in range(min(args.steps, 3)):
-                    hg = lm.expmap(metric, m, num_steps=E, phiinv=z)
-                torch.cuda.synchronize()
-                t_general = (time.perf_counter() - tg0) / min(args.steps, 3)
-                same_bits = bool(torch.equal(hg, h))
-                del hg, z
-        finally:
-            _lddmm.EXPMAP_STREAMS = default_streams
+        if args.dump_outputs and rank == 0:
+            dump_outputs(args.dump_outputs, h)
+        t_single = single_bits = t_general = same_bits = None
+        ksum = {}
+        if args.full:
+            # ROOFLINE PASS (same process, same inputs, right after the timed region): the same shoots
+            # on ONE stream, so that a launch's HIP-event duration is the time the kernel needs by itself.  `roofline`
+            # and `single_stream` below come from here; the headline does not.
+            _lddmm.EXPMAP_STREAMS = 1
+            try:
+                with KernelTimer(ext, names) as kt1:
+                    step()
+                    torch.cuda.synchronize()
+                    kt1.enabled = True
+                    ts0 = time.perf_counter()
+                    for _ in range(args.steps):
+                        h1 = step()
+                    torch.cuda.synchronize()
+                    t_single = (time.perf_counter() - ts0) / args.steps
+                    kt1.enabled = False
+                    ksum = kt1.summary()
+                single_bits = bool(torch.equal(h1, h))
+                del h1
+                # for comparison, untimed: the same single-stream shoot with every Euler step through the general
+                # kernels (an explicit zero phiinv switches off the closed-form first step; same result bit for bit)
+                if not args.no_extras:
+                    z = torch.zeros_like(m)
+                    lm.expmap(metric, m, num_steps=E, phiinv=z)
+                    torch.cuda.synchronize()
+                    tg0 = time.perf_counter()
+                    for _ in range(min(args.steps, 3)):
+                        hg = lm.expmap(metric, m, num_steps=E, phiinv=z)
+                    torch.cuda.synchronize()
+                    t_general = (time.perf_counter() - tg0) / min(args.steps, 3)
+                    same_bits = bool(torch.equal(hg, h))
+                    del hg, z
+            finally:
+                _lddmm.EXPMAP_STREAMS = default_streams
         split_active = default_streams >= 2 and B // _lddmm.EXPMAP_MIN_ITEMS >= default_streams   # (lddmm._shoot_forward_split)
         del h
     elapsed = torch.tensor([t1 - t0], device=dev, dtype=torch.float64)
@@ -991,30 +1032,32 @@ def main():
                            f"one HIP stream (the sub-batch split needs {max(2, 2 * _lddmm.EXPMAP_MIN_ITEMS)}+ items per rank "
                            "and lddmm.EXPMAP_STREAMS >= 2)"),
             "streams": default_streams if split_active else 1,
-            "single_stream": {"ms_per_step": 1e3 * t_single, "same_bits": single_bits,
-                              "note": "the same shoots with lddmm.EXPMAP_STREAMS = 1, after the timed region: the pass "
-                                      "the roofline object's launch durations are measured in"},
-            "all_steps_through_the_general_kernels": None if t_general is None else {
-                "ms_per_step": 1e3 * t_general, "local_voxel_steps_per_s": B * S ** 3 * E / t_general, "same_bits": same_bits},
             "global_batch": GBATCH, "per_gpu_batch": B, "volume": [S, S, S], "euler_steps": E,
             "parallelism": f"batch-sharded x{world}, no data-path collective in expmap; the atlas step "
                            "(atlas_step below) all-reduces the atlas gradient over RCCL",
             "max_abs_displacement_vox": hmax,
         },
     }
+    if args.full:
+        result["config"]["single_stream"] = {
+            "ms_per_step": 1e3 * t_single, "same_bits": single_bits,
+            "note": "the same shoots with lddmm.EXPMAP_STREAMS = 1, after the timed region: the pass the roofline "
+                    "object's launch durations are measured in"}
+        result["config"]["all_steps_through_the_general_kernels"] = None if t_general is None else {
+            "ms_per_step": 1e3 * t_general, "local_voxel_steps_per_s": B * S ** 3 * E / t_general, "same_bits": same_bits}
     del m
     torch.cuda.empty_cache()
     atlas, epoch = None, None
-    if not args.no_atlas:
+    if args.full and not args.no_atlas:
         atlas = atlas_leg(lm, dev, world, rank, args, force_dist=force_dist)
-    if not args.no_epoch:
+    if args.full and not args.no_epoch:
         epoch = atlas_epoch_leg(lm, dev, world, rank, args, force_dist=force_dist)
     if rank == 0:
         if atlas is not None:
             result["atlas_step"] = atlas
         if epoch is not None:
             result["atlas_epoch"] = epoch
-        if world == 1:
+        if world == 1 and args.full:
             result["rccl_world_size_1"] = {"requested": FORCE_DIST, "active": force_dist, "detail": force_dist_detail}
         # the dominant single kernel of the timed region (fluid_metric is three kernels and is reported
         # separately): all four candidates move 36 algorithmic bytes per voxel at C = 3
@@ -1066,9 +1109,10 @@ def main():
         result["breakdown_ms_per_step"]["note"] = ("timed region; sums of per-launch HIP-event durations over BOTH streams "
                                                    "(they overlap in time, so they add up to more than the wall)"
                                                    if split_active else "timed region, one stream")
-        result["breakdown_ms_per_step_single_stream"] = {n: s["total_ms"] / args.steps for n, s in ksum.items()}
-        result["breakdown_ms_per_step_single_stream"]["wall"] = 1e3 * t_single
-        if not args.no_micro and world == 1:
+        if args.full:
+            result["breakdown_ms_per_step_single_stream"] = {n: s["total_ms"] / args.steps for n, s in ksum.items()}
+            result["breakdown_ms_per_step_single_stream"]["wall"] = 1e3 * t_single
+        if args.full and not args.no_micro and world == 1:
             result["interp_splat"] = micro_interp_splat(ext, dev, S)
             torch.cuda.empty_cache()
             result["fluid"] = micro_fluid(lm, dev, S)
@@ -1079,7 +1123,7 @@ def main():
             torch.cuda.empty_cache()
             result["brain_grid"] = micro_brain_grid(lm, dev)
             torch.cuda.empty_cache()
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             result["cpu_baseline"] = cpu_baseline(S, E, args.cpu_sample_batch)
             try:
                 result["cpu_baseline"]["reference_cpu_path"] = reference_cpu_path(lm, dev, S)

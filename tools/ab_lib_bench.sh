@@ -1,13 +1,15 @@
 #!/bin/bash
 # usage (GPU box): tools/ab_lib_bench.sh tagA tagB ...  -- bench.py (micro ops, atlas steps) per library build ab_<tag>.so, one line each
+# (JSON lines under $LAGO_OUT_DIR/abbench, default out/abbench)
 cd "$(dirname "$0")/.."
-mkdir -p gpurun_out/abbench
+out=${LAGO_OUT_DIR:-out}/abbench
+mkdir -p $out
 for v in "$@"; do
-  LAGO_HIP_LIBRARY=$PWD/lagomorph_amd/_lib/ab_$v.so timeout 400 python bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-extras --atlas-steps 3 > gpurun_out/abbench/$v.json 2> gpurun_out/abbench/$v.err < /dev/null
-  python3 - "$v" <<'PY'
+  LAGO_HIP_LIBRARY=$PWD/lagomorph_amd/_lib/ab_$v.so timeout 400 python bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-extras --atlas-steps 3 > $out/$v.json 2> $out/$v.err < /dev/null
+  python3 - "$v" "$out/$v.json" <<'PY'
 import json, sys
 v = sys.argv[1]
-d = json.loads(open(f"gpurun_out/abbench/{v}.json").read().strip().splitlines()[-1])
+d = json.loads(open(sys.argv[2]).read().strip().splitlines()[-1])
 o = d["other_ops"]["ops"]
 us = lambda k: round(o[k]["ms"] * 1e3, 1)
 print(f"{v:>6s}: shoot {d['ms_per_step']:.2f} atlas160 {d['atlas_step']['ms_per_step']:.2f} atlas128 {d['atlas_step_128']['ms']:.3f} | pair {d['interp_splat']['smooth']['pair_ms']*1e3:.1f} fwd {d['interp_splat']['smooth']['fwd_ms']*1e3:.1f} bwd {d['interp_splat']['smooth']['bwd_lds_ms']*1e3:.1f} | "

@@ -7,7 +7,7 @@ mkdir -p gpurun_out/abtrace
 for v in "$@"; do
   out=gpurun_out/abtrace/$v
   rm -rf $out
-  LAGO_HIP_LIBRARY=$PWD/lagomorph_amd/_lib/ab_$v.so timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $out -- python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-micro --no-atlas --no-extras > $out.json 2> $out.err < /dev/null
+  LAGO_HIP_LIBRARY=$PWD/lagomorph_amd/_lib/ab_$v.so timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $out -- python3 bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-micro --no-atlas --no-extras > $out.json 2> $out.err < /dev/null
   f=$(find $out -name "*kernel_stats.csv" | head -1)
   echo "== $v  $(python3 -c "import json,sys; d=json.loads(open('$out.json').read().strip().splitlines()[-1]); print('ms_per_step', round(d['ms_per_step'],3))" 2>/dev/null)"
   if [ -n "$f" ]; then python3 tools/rocprof_summary.py "$f" | sed -n 3,7p | cut -c1-110; fi
