@@ -232,7 +232,22 @@ long long lago_reversed_launches(void);
     int lago_regrid_backward_sep##SUF(REAL *d_I, const REAL *grad_out, REAL *ws, int64_t ws_elems, int dim,         \
                                       int64_t nn, int64_t nc, int64_t nx, int64_t ny, int64_t nz, int64_t Nx,       \
                                       int64_t Ny, int64_t Nz, const double *origin, const double *spacing,          \
-                                      void *stream);
+                                      void *stream);                                                                \
+    /* jacobian_determinant: out = det J, J[c][a] = D_a u_c (+ 1 when displacement and a == c) with the clamped     \
+     * central difference of lago_jtv_forward (a one-sided half difference at the borders, zero along an axis of    \
+     * extent 1; the 1 is added to the rounded difference).  u: (nn, dim, sp), out: (nn, 1, sp).  Every product and \
+     * sum is rounded on its own, in this order:                                                                    \
+     *   2D: J00*J11 - J01*J10                                                                                      \
+     *   3D: (J00*(J11*J22 - J12*J21) - J01*(J10*J22 - J12*J20)) + J02*(J10*J21 - J11*J20)                          \
+     * No counterpart in the reference. */                                                                          \
+    int lago_jacdet_forward##SUF(REAL *out, const REAL *u, int displacement, int dim, int64_t nn, int64_t nx,       \
+                                 int64_t ny, int64_t nz, void *stream);                                             \
+    /* its gradient: d_u[c] = sum_a D_a^T (grad_out * C[c][a]), C[c][a] = d det / d J[c][a] the cofactor matrix     \
+     * and D_a^T the adjoint stencil of lago_jtv_adjoint_forward.  grad_out: (nn, 1, sp), d_u like u.  One gather   \
+     * pass without atomics: every element of d_u is written once, identically from run to run.  No counterpart in  \
+     * the reference. */                                                                                            \
+    int lago_jacdet_backward##SUF(REAL *d_u, const REAL *grad_out, const REAL *u, int displacement, int dim,        \
+                                  int64_t nn, int64_t nx, int64_t ny, int64_t nz, void *stream);
 
 LAGO_DECLARE(float, _f32)
 LAGO_DECLARE(double, _f64)

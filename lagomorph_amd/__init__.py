@@ -16,8 +16,9 @@ if not _BUILDING:
                          affine_inverse, det_2x2, invert_2x2, invert_3x3, regrid, rigid_inverse, rotation_exp_map)
     from .deform import (InterpFunction, compose, compose_disp_vel, compose_vel_disp, identity, interp,  # noqa: F401
                          interp_hessian_diagonal_image)
-    from .diff import (JacobianTimesVectorFieldAdjointFunction, JacobianTimesVectorFieldFunction,  # noqa: F401
-                       jacobian_times_vectorfield, jacobian_times_vectorfield_adjoint)
+    from .diff import (JacobianDeterminantFunction, JacobianTimesVectorFieldAdjointFunction,  # noqa: F401
+                       JacobianTimesVectorFieldFunction, jacobian_determinant, jacobian_times_vectorfield,
+                       jacobian_times_vectorfield_adjoint)
     from .lagomorph_ext import set_debug_mode  # noqa: F401
     from .lddmm import EPDiff_step, LDDMMAtlasBuilder, expmap, expmap_advect, lddmm_step, shard_indices  # noqa: F401
     from .metric import FluidMetric, FluidMetricOperator, Metric  # noqa: F401

@@ -296,6 +296,108 @@ __global__ __launch_bounds__(kBlock) void jtv_adj_bwd_kernel(R *__restrict__ d_v
     for (int d = 0; d < DIM; ++d) st_pol<LAGO_NT_STENCIL_BWD_ST>(&dwn[(size_t)d * nv], (R)(dw[d]));
 }
 
+// ------------------------------------------------------------------ det(Du + delta) and its gradient
+//
+// No counterpart in the reference.  J[c][a] = D_a u_c (+ 1 on the diagonal in displacement mode) is the value
+// jtv_fwd_kernel forms (st.grad, the one added to the rounded difference); an axis of extent 1 has plus == minus == 0
+// and hence a zero difference.  Every product and sum is rounded on its own (-ffp-contract=off), in the order written
+// in include/lagomorph_hip.h, so that a numpy restatement in the same precision gives the same bits.
+
+template <typename R, int DIM>
+__device__ __forceinline__ R det_of(const R (&J)[DIM][DIM]) {
+    if constexpr (DIM == 2) {
+        return J[0][0] * J[1][1] - J[0][1] * J[1][0];
+    } else {
+        return (J[0][0] * (J[1][1] * J[2][2] - J[1][2] * J[2][1]) - J[0][1] * (J[1][0] * J[2][2] - J[1][2] * J[2][0])) +
+               J[0][2] * (J[1][0] * J[2][1] - J[1][1] * J[2][0]);
+    }
+}
+
+// 16 bytes per voxel (float32, 3D): the 18 neighbour loads of u, one store; nothing intermediate is written.
+template <typename R, int DIM, bool DISP>
+__global__ __launch_bounds__(kBlock) void jacdet_fwd_kernel(R *__restrict__ out, const R *__restrict__ u, Geom g) {
+    const Vox vx = locate(g);
+    if (!vx.valid) return;
+    const size_t nv = g.nvox;
+    const Stencil<DIM> st(g, vx);
+    const R *un = u + (size_t)vx.n * DIM * nv + vx.s;
+    R J[DIM][DIM];
+#pragma unroll
+    for (int c = 0; c < DIM; ++c) {
+        st.grad(un + (size_t)c * nv, J[c]);
+        if (DISP) J[c][c] = J[c][c] + (R)1.0;
+    }
+    st_pol<LAGO_NT_STENCIL_FWD_ST>(&out[(size_t)vx.n * nv + vx.s], (R)(det_of<R, DIM>(J)));
+}
+
+// d_u[c] = sum_a D_a^T (grad_out * C[c][a]), C the cofactor matrix of J, in gather form: the lane that owns voxel x
+// evaluates column a of C at the two clamped neighbours y = clamp(x +- e_a) and applies the three-case adjoint stencil
+// to the products.  At a border the clamped neighbour IS x, which is exactly the voxel's own term of that case
+// (Stencil::dTv), so the two evaluation points serve all three cases without a branch around the loads.  Column a of C
+// holds no derivative along a: the loads are u at x +- e_a +- e_b (b != a), every one of them inside the grid because y
+// shares x's position on the axes b, and grad_out at x +- e_a.  No atomics, nothing intermediate in memory, every
+// element of d_u written once by its own lane: the result does not depend on the launch.
+template <typename R, int DIM, bool DISP>
+__global__ __launch_bounds__(kBlock) void jacdet_bwd_kernel(R *__restrict__ d_u, const R *__restrict__ go,
+                                                            const R *__restrict__ u, Geom g) {
+    const Vox vx = locate(g);
+    if (!vx.valid) return;
+    const size_t nv = g.nvox;
+    const Stencil<DIM> st(g, vx);
+    const R *un = u + (size_t)vx.n * DIM * nv + vx.s;
+    const R *gon = go + (size_t)vx.n * nv + vx.s;
+    R *dn = d_u + (size_t)vx.n * DIM * nv + vx.s;
+    R acc[DIM];
+#pragma unroll
+    for (int c = 0; c < DIM; ++c) acc[c] = 0;
+#pragma unroll
+    for (int a = 0; a < DIM; ++a) {
+        R C[2][DIM], gv[2];   // [0]: at the clamped +1 neighbour along a, [1]: at the clamped -1 neighbour
+#pragma unroll
+        for (int sg = 0; sg < 2; ++sg) {
+            const int o = sg == 0 ? st.plus[a] : st.minus[a];
+            gv[sg] = gon[o];
+            if constexpr (DIM == 3) {
+                const int b1 = (a + 1) % 3, b2 = (a + 2) % 3;
+                R d1[3], d2[3];   // J[r][b1], J[r][b2] at y
+#pragma unroll
+                for (int r = 0; r < 3; ++r) {
+                    const R *ur = un + (size_t)r * nv;
+                    d1[r] = (R)0.5f * (ur[o + st.plus[b1]] - ur[o + st.minus[b1]]);
+                    d2[r] = (R)0.5f * (ur[o + st.plus[b2]] - ur[o + st.minus[b2]]);
+                    if (DISP && r == b1) d1[r] = d1[r] + (R)1.0;
+                    if (DISP && r == b2) d2[r] = d2[r] + (R)1.0;
+                }
+#pragma unroll
+                for (int c = 0; c < 3; ++c) {
+                    const int c1 = (c + 1) % 3, c2 = (c + 2) % 3;
+                    C[sg][c] = d1[c1] * d2[c2] - d2[c1] * d1[c2];
+                }
+            } else {
+                const int b = 1 - a;
+#pragma unroll
+                for (int c = 0; c < 2; ++c) {   // C[c][a] = +-J[1 - c][1 - a]
+                    const R *ur = un + (size_t)(1 - c) * nv;
+                    R d = (R)0.5f * (ur[o + st.plus[b]] - ur[o + st.minus[b]]);
+                    if (DISP && 1 - c == b) d = d + (R)1.0;
+                    C[sg][c] = c == a ? d : -d;
+                }
+            }
+        }
+        if (st.len[a] == 1) continue;   // zero difference, zero adjoint (deviations)
+#pragma unroll
+        for (int c = 0; c < DIM; ++c) {
+            R t;
+            if (st.pos[a] == 0) t = (R)(-.5) * lg_fma(C[1][c], gv[1], C[0][c] * gv[0]);
+            else if (st.pos[a] == st.len[a] - 1) t = (R)(.5) * lg_fma(C[0][c], gv[0], C[1][c] * gv[1]);
+            else t = (R)(-.5) * lg_fma(C[0][c], gv[0], -(C[1][c] * gv[1]));
+            acc[c] = acc[c] + t;
+        }
+    }
+#pragma unroll
+    for (int c = 0; c < DIM; ++c) st_pol<LAGO_NT_STENCIL_BWD_ST>(&dn[(size_t)c * nv], (R)(acc[c]));
+}
+
 // ------------------------------------------------------------------ host entry points
 
 static bool thin(int dim, int64_t nx, int64_t ny, int64_t nz) {
@@ -416,6 +518,33 @@ static int jtv_adjoint_backward_impl(R *d_v, R *d_w, const R *go, const R *v, co
     return finish_launch(s, "jacobian_times_vectorfield_adjoint_backward");
 }
 
+// forward: aux == nullptr, out = det; backward: out = d_u, aux = grad_out
+template <typename R>
+static int jacdet_impl(R *out, const R *aux, const R *u, bool backward, int disp, int dim, int64_t nn, int64_t nx,
+                       int64_t ny, int64_t nz, void *stream) {
+    const char *what = backward ? "jacobian_determinant_backward" : "jacobian_determinant_forward";
+    if (dim != 2 && dim != 3) return fail_invalid("Only two- and three-dimensional jacobian determinant is supported");
+    Geom g;
+    if (!make_geom(g, dim, nn, nx, ny, nz)) return fail_invalid("%s: bad extent", what);
+    if (g.nblocks == 0) return LAGO_OK;
+    if (!out || !u || (backward && !aux)) return fail_invalid("%s: null pointer", what);
+    hipStream_t s = (hipStream_t)stream;
+#define LAUNCH(D, DS)                                                                                               \
+    do {                                                                                                            \
+        if (backward)                                                                                               \
+            hipLaunchKernelGGL((jacdet_bwd_kernel<R, D, DS>), dim3(g.nblocks), dim3(kBlock), 0, s, out, aux, u, g); \
+        else                                                                                                        \
+            hipLaunchKernelGGL((jacdet_fwd_kernel<R, D, DS>), dim3(g.nblocks), dim3(kBlock), 0, s, out, u, g);      \
+    } while (0)
+    if (dim == 3) {
+        if (disp) LAUNCH(3, true); else LAUNCH(3, false);
+    } else {
+        if (disp) LAUNCH(2, true); else LAUNCH(2, false);
+    }
+#undef LAUNCH
+    return finish_launch(s, what);
+}
+
 }  // namespace lago
 
 extern "C" {
@@ -443,6 +572,14 @@ extern "C" {
     int lago_jtv_adjoint_backward##SUF(REAL *d_v, REAL *d_w, const REAL *go, const REAL *v, const REAL *w,         \
                                        int dim, int64_t nn, int64_t nx, int64_t ny, int64_t nz, void *stream) {    \
         return lago::jtv_adjoint_backward_impl<REAL>(d_v, d_w, go, v, w, dim, nn, nx, ny, nz, stream);             \
+    }                                                                                                               \
+    int lago_jacdet_forward##SUF(REAL *out, const REAL *u, int displacement, int dim, int64_t nn, int64_t nx,      \
+                                 int64_t ny, int64_t nz, void *stream) {                                           \
+        return lago::jacdet_impl<REAL>(out, nullptr, u, false, displacement, dim, nn, nx, ny, nz, stream);         \
+    }                                                                                                               \
+    int lago_jacdet_backward##SUF(REAL *d_u, const REAL *grad_out, const REAL *u, int displacement, int dim,       \
+                                  int64_t nn, int64_t nx, int64_t ny, int64_t nz, void *stream) {                  \
+        return lago::jacdet_impl<REAL>(d_u, grad_out, u, true, displacement, dim, nn, nx, ny, nz, stream);         \
     }
 LAGO_DEFINE(float, _f32)
 LAGO_DEFINE(double, _f64)

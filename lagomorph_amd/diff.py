@@ -4,6 +4,7 @@ Host-side mirror of ``/root/reference/lagomorph/diff.py``; kernels in
 ``csrc/diff.hip``.
 """
 import torch
+from torch.autograd.function import once_differentiable
 
 from . import lagomorph_ext
 
@@ -50,3 +51,26 @@ class JacobianTimesVectorFieldAdjointFunction(torch.autograd.Function):
 
 
 jacobian_times_vectorfield_adjoint = JacobianTimesVectorFieldAdjointFunction.apply
+
+
+class JacobianDeterminantFunction(torch.autograd.Function):
+    """det(Du [+ I]) with the clamped central differences of jacobian_times_vectorfield, one fused kernel each way.
+    Not in the reference."""
+
+    @staticmethod
+    def forward(ctx, u, displacement):
+        ctx.displacement = displacement
+        ctx.save_for_backward(u)
+        return lagomorph_ext.jacobian_determinant_forward(u, displacement)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gradout):
+        (u,) = ctx.saved_tensors
+        return lagomorph_ext.jacobian_determinant_backward(gradout, u, ctx.displacement), None
+
+
+def jacobian_determinant(u, displacement=True):
+    """Jacobian determinant of x -> x + u(x) (displacement=True) or of u itself, as an image (N, 1, *sp): the volume
+    change of the deformation, <= 0 where it folds.  u: (N, d, *sp), d = len(sp) in {2, 3}."""
+    return JacobianDeterminantFunction.apply(u, displacement)

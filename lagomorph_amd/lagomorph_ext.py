@@ -69,6 +69,8 @@ _SIGS = {
                                    _dbl, _vp],
     "lago_jtv_backward_acc": [_vp, _vp, _vp, _vp, _vp, _int, _int, _int, _i64, _i64, _i64, _i64, _i64, _int, _vp],
     "lago_ad_star": [_vp, _vp, _vp, _int, _i64, _i64, _i64, _i64, _vp],
+    "lago_jacdet_forward": [_vp, _vp, _int, _int, _i64, _i64, _i64, _i64, _vp],
+    "lago_jacdet_backward": [_vp, _vp, _vp, _int, _int, _i64, _i64, _i64, _i64, _vp],
     "lago_fluid_metric": [_vp, _vp, _vp, _i64, _int, _vp, _vp, _vp, _vp, _vp, _vp, _dbl, _dbl, _dbl, _int, _i64, _i64,
                           _i64, _i64, _vp],
     "lago_fluid_metric_scaled": [_vp, _vp, _vp, _i64, _int, _vp, _vp, _vp, _vp, _vp, _vp, _dbl, _dbl, _dbl, _int, _i64,
@@ -438,6 +440,42 @@ def jacobian_times_vectorfield_adjoint_backward(grad_out, v, w, need_v, need_w):
     _call("lago_jtv_adjoint_backward", v, _ptr(d_v), _ptr(d_w), _ptr(grad_out), _ptr(v), _ptr(w), dim, v.size(0), nx,
           ny, nz)
     return [d_v, d_w]
+
+
+def _check_jacdet(u):
+    if not isinstance(u, torch.Tensor) or not u.is_cuda:
+        raise RuntimeError("u must be a CUDA tensor")
+    _suffix(u)
+    dim, nx, ny, nz = _spatial(u)
+    if dim not in (2, 3):
+        raise RuntimeError("Only two- and three-dimensional jacobian determinant is supported")
+    if u.size(1) != dim:
+        raise RuntimeError("jacobian determinant is only defined for vector fields")
+    return dim, nx, ny, nz
+
+
+def jacobian_determinant_forward(u, displacement):
+    """det(Du + [displacement] I) with the clamped central differences of jacobian_times_vectorfield_forward, as an
+    image (N, 1, *sp).  Not in the reference (csrc/diff.hip: jacdet_fwd_kernel)."""
+    dim, nx, ny, nz = _check_jacdet(u)
+    u = u.contiguous()
+    out = torch.empty((u.size(0), 1) + tuple(u.shape[2:]), dtype=u.dtype, device=u.device)
+    _call("lago_jacdet_forward", u, _ptr(out), _ptr(u), int(bool(displacement)), dim, u.size(0), nx, ny, nz)
+    return out
+
+
+def jacobian_determinant_backward(grad_out, u, displacement):
+    """d_u of jacobian_determinant_forward for grad_out of shape (N, 1, *sp): one gather pass, no atomics
+    (csrc/diff.hip: jacdet_bwd_kernel)."""
+    dim, nx, ny, nz = _check_jacdet(u)
+    _check_jtv(u, grad_out)
+    if tuple(grad_out.shape) != (u.size(0), 1) + tuple(u.shape[2:]):
+        raise RuntimeError("jacobian_determinant_backward: grad_out must have shape (N, 1, *spatial)")
+    grad_out, u = grad_out.contiguous(), u.contiguous()
+    d_u = torch.empty_like(u)
+    _call("lago_jacdet_backward", u, _ptr(d_u), _ptr(grad_out), _ptr(u), int(bool(displacement)), dim, u.size(0), nx,
+          ny, nz)
+    return d_u
 
 
 def fluid_operator(Fmv, inverse, cosluts, sinluts, alpha, beta, gamma):
