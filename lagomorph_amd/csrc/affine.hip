@@ -15,6 +15,7 @@
 #include <algorithm>
 
 #include "common.hpp"
+#include "affine_box.hpp"   // half_extent, the box kernel's candidate / ownership functions
 
 #ifndef LAGO_NT_AFFINE_ST
 #define LAGO_NT_AFFINE_ST 0
@@ -29,11 +30,6 @@ int affine_splat_lds(R *d_I, const R *go, const R *A, const R *T, int nc, int64_
 template <typename R>
 int regrid_splat_lds(R *d_I, const R *go, int64_t nplanes, const Geom &g, const Geom &gs, const double *O,
                      const double *S, hipStream_t s);
-
-template <typename R>
-__device__ __forceinline__ R half_extent(int n) {  // `.5*static_cast<Real>(n-1)`, cuda/affine.cu:42-43
-    return (R)(.5 * (double)(R)(n - 1));
-}
 
 // ------------------------------------------------------------------ affine forward
 
@@ -198,9 +194,10 @@ void tune_affine(int box) { g_affine_box = box ? 1 : 0; }
 // (cuda/affine.cu:42-61), so every contribution is made once.  Their eight cells are the box plus one layer on its
 // upper faces: the LDS window is (BX + 1)(BY + 1)(BZ + 1) cells, nothing ever misses it, and the flush touches 1.3
 // cells per voxel instead of the bounding box of a sheared tile.  Candidates: the source voxels in the bounding box of
-// the box's PREIMAGE (the inverse matrix in double, one voxel of slack for the rounding of h; border boxes own
-// everything clamped onto them and reach out to the image of the source grid's corners).  Matrices whose inverse would
-// make that candidate set large (or that have none) are left, per batch item and decided on the device, to the general
+// the box's PREIMAGE (the inverse matrix in double, widened by affine_box_slack -- a few hundredths of a voxel -- for the
+// rounding of h; border boxes own everything clamped onto them and reach out to the image of the source grid's
+// corners; affine_box.hpp, walked on the host by tests/test_affine_box_cover.py).  Matrices whose inverse would make
+// that candidate set large (or that have none) are left, per batch item and decided on the device, to the general
 // kernel (common.hpp: affine_item_regular).  d_I as always: float64 sums per window, one float atomic per touched cell.
 #ifndef LAGO_BOX_ROWS
 #define LAGO_BOX_ROWS 3   // candidate rows a wave of affine_splat_box_kernel keeps in flight (1: 231, 2: 227, 3: 222, 4: 224 us at 8 x 128^3)
@@ -234,57 +231,14 @@ __global__ __launch_bounds__(kBlock) void affine_splat_box_kernel(R *__restrict_
     const R ox = half_extent<R>(nx), oy = half_extent<R>(ny), oz = half_extent<R>(nz);
     const double od[3] = {(double)ox, (double)oy, (double)oz};
     const double Td[3] = {(double)Tn[0], (double)Tn[1], (double)Tn[2]};
-    // the box in position space: [lo, hi) per axis; a border box owns everything clamped onto it, i.e. it reaches to
-    // the image of the source grid (its eight corners) on that side
-    double lo[3] = {(double)X0, (double)Y0, (double)Z0}, hi[3] = {(double)(X0 + ex), (double)(Y0 + ey), (double)(Z0 + ez)};
-    {
-        double hmin[3] = {1e300, 1e300, 1e300}, hmax[3] = {-1e300, -1e300, -1e300};
-        const int ext[3] = {nx, ny, nz};
-#pragma unroll
-        for (int q = 0; q < 8; ++q) {
-            const double f[3] = {((q & 4) ? ext[0] - 1 : 0) - od[0], ((q & 2) ? ext[1] - 1 : 0) - od[1], ((q & 1) ? ext[2] - 1 : 0) - od[2]};
-#pragma unroll
-            for (int d = 0; d < 3; ++d) {
-                const double h = (double)An[3 * d] * f[0] + (double)An[3 * d + 1] * f[1] + (double)An[3 * d + 2] * f[2] + Td[d] + od[d];
-                hmin[d] = h < hmin[d] ? h : hmin[d];
-                hmax[d] = h > hmax[d] ? h : hmax[d];
-            }
-        }
-        const int org[3] = {X0, Y0, Z0}, len[3] = {ex, ey, ez};
-#pragma unroll
-        for (int d = 0; d < 3; ++d) {
-            if (org[d] == 0) lo[d] = fmin(lo[d], hmin[d] - 2.0);
-            if (org[d] + len[d] == ext[d]) hi[d] = fmax(hi[d], hmax[d] + 2.0);
-        }
-    }
-    // candidate sources: bounding box of the preimage of [lo, hi), one voxel of slack, inside the grid
+    // (affine_box.hpp) the box in position space, border boxes reaching out to the image of the source grid's corners; then
+    // the candidate sources: bounding box of its preimage, widened by affine_box_slack, inside the grid
+    const int ext[3] = {nx, ny, nz}, org[3] = {X0, Y0, Z0}, len[3] = {ex, ey, ez};
+    double lo[3], hi[3], mn[3], mx[3];
     int s0[3], s1[3];
-    {
-        double mn[3] = {1e300, 1e300, 1e300}, mx[3] = {-1e300, -1e300, -1e300};
-#pragma unroll
-        for (int q = 0; q < 8; ++q) {
-            const double h[3] = {((q & 4) ? hi[0] : lo[0]) - Td[0] - od[0], ((q & 2) ? hi[1] : lo[1]) - Td[1] - od[1],
-                                 ((q & 1) ? hi[2] : lo[2]) - Td[2] - od[2]};
-#pragma unroll
-            for (int d = 0; d < 3; ++d) {
-                const double x = Ai[3 * d] * h[0] + Ai[3 * d + 1] * h[1] + Ai[3 * d + 2] * h[2] + od[d];
-                mn[d] = x < mn[d] ? x : mn[d];
-                mx[d] = x > mx[d] ? x : mx[d];
-            }
-        }
-        const int ext[3] = {nx, ny, nz};
-#pragma unroll
-        for (int d = 0; d < 3; ++d) {
-            // slack for the float rounding of h and of the inverse, NOT a whole voxel per side: inside the grid |h| is below
-            // the extent n, so h is off by at most ~6 float ulps of n = 3.6e-7 n, and the rows of |A^-1| sum to at most 4
-            // (affine_item_regular): 1.5e-6 n voxels in source coordinates.  0.02 + 1e-5 n leaves a factor of seven.  A box of
-            // 8 x 8 x 48 cells then has about 1.45 instead of 2.0 candidates per owned voxel (-9 % on the kernel,
-            // profiles/r06_ab_box_slack.txt); border boxes reach out to the image of the grid's corners as before.
-            const double slack = 0.02 + 1e-5 * (double)max(nx, max(ny, nz));
-            s0[d] = max(0, (int)floor(fmax(mn[d] - slack, -1e9)));
-            s1[d] = min(ext[d] - 1, (int)ceil(fmin(mx[d] + slack, 1e9)));
-        }
-    }
+    affine_box_interval<R>(An, Td, od, ext, org, len, lo, hi);
+    affine_box_preimage(Ai, Td, od, lo, hi, mn, mx);
+    affine_box_candidates(mn, mx, affine_box_slack(nx, ny, nz), ext, s0, s1);
     const int WY = bg.BY + 1, WZ = bg.BZ + 1;
     const int wcells = (bg.BX + 1) * WY * WZ;
     for (int f = threadIdx.x; f < wcells; f += kBlock) win[f] = 0.0;
@@ -316,13 +270,11 @@ __global__ __launch_bounds__(kBlock) void affine_splat_box_kernel(R *__restrict_
                     const int row = row0 + q * (kBlock / 64);
                     const int i = s0[0] + row / cy, j = s0[1] + row % cy;   // (scalar)
                     const R fi = (R)i - ox, fj = (R)j - oy;
-                    // cuda/affine.cu:42-61 (as affine_bwd_kernel above)
-                    hx[q] = lg_fma(An[2], fk, lg_fma(An[0], fi, An[1] * fj)) + Tn[0] + ox;
-                    hy[q] = lg_fma(An[5], fk, lg_fma(An[3], fi, An[4] * fj)) + Tn[1] + oy;
-                    hz[q] = lg_fma(An[8], fk, lg_fma(An[6], fi, An[7] * fj)) + Tn[2] + oz;
-                    fx[q] = lg_floor(hx[q]); fy[q] = lg_floor(hy[q]); fz[q] = lg_floor(hz[q]);
-                    lx[q] = (uint32_t)(clamp1(fx[q], nx) - X0); ly[q] = (uint32_t)(clamp1(fy[q], ny) - Y0); lz[q] = (uint32_t)(clamp1(fz[q], nz) - Z0);
-                    own[q] = row < rows && k <= s1[2] && lx[q] < (uint32_t)ex && ly[q] < (uint32_t)ey && lz[q] < (uint32_t)ez;   // else: another box owns it
+                    // cuda/affine.cu:42-61 (as affine_bwd_kernel above), floor cell, ownership: affine_box.hpp
+                    affine_box_position<R>(An, Tn, fi, fj, fk, ox, oy, oz, hx[q], hy[q], hz[q]);
+                    const bool mine = affine_box_owns<R>(hx[q], hy[q], hz[q], nx, ny, nz, X0, Y0, Z0, ex, ey, ez, fx[q], fy[q], fz[q],
+                                                         lx[q], ly[q], lz[q]);
+                    own[q] = row < rows && k <= s1[2] && mine;
                     const uint32_t off = (uint32_t)((((size_t)i * ny + j) * nz + k) * sizeof(R));
                     diff[q] = buf_load1<R>(rgo, own[q] ? off : 0xffffffffu);
                 }

@@ -184,24 +184,37 @@ __device__ __forceinline__ Vox locate(const Geom &g) {
 // contraction nvcc applies by default to the reference.  The CPU oracle spells
 // out the identical pattern (oracle/lago_oracle_impl.h, LG_FMA), and the library
 // is compiled with -ffp-contract=off so that nothing else fuses.
-__device__ __forceinline__ float lg_fma(float a, float b, float c) { return __builtin_fmaf(a, b, c); }
-__device__ __forceinline__ double lg_fma(double a, double b, double c) { return __builtin_fma(a, b, c); }
+// (__host__ too, like lg_floor and clamp1 below: tests/native/affine_box_emul.hip runs affine_box.hpp on the CPU)
+__host__ __device__ __forceinline__ float lg_fma(float a, float b, float c) { return __builtin_fmaf(a, b, c); }
+__host__ __device__ __forceinline__ double lg_fma(double a, double b, double c) { return __builtin_fma(a, b, c); }
 
 // include/interp.h:64-70: (int)x, minus one for negative non-integers == floor(x).
 // Saturated to +-2^30 (as the oracle does) so that floor + 1 cannot overflow.
 // float: one v_cvt_flr_i32_f32 (floor + convert, saturating at the int32 range) and one
 // v_med3_i32 -- the same value as saturating first, for every finite x.
-__device__ __forceinline__ int lg_med3(int x, int lo, int hi) {  // lo <= hi
+// The host branches (as FastDiv::div has one) give the same value for every input, NaN included (-> 0).
+__host__ __device__ __forceinline__ int lg_med3(int x, int lo, int hi) {  // lo <= hi
+#if defined(__HIP_DEVICE_COMPILE__)
     int r;
     asm("v_med3_i32 %0, %1, %2, %3" : "=v"(r) : "v"(x), "v"(lo), "v"(hi));
     return r;
+#else
+    return x < lo ? lo : (x > hi ? hi : x);
+#endif
 }
-__device__ __forceinline__ int lg_floor(float x) {
+__host__ __device__ __forceinline__ int lg_floor(float x) {
+#if defined(__HIP_DEVICE_COMPILE__)
     int r;
     asm("v_cvt_flr_i32_f32 %0, %1" : "=v"(r) : "v"(x));
     return lg_med3(r, -1073741824, 1073741824);
+#else
+    if (!(x == x)) return 0;
+    x = x > 1073741824.0f ? 1073741824.0f : x;
+    x = x < -1073741824.0f ? -1073741824.0f : x;
+    return (int)__builtin_floorf(x);
+#endif
 }
-__device__ __forceinline__ int lg_floor(double x) {
+__host__ __device__ __forceinline__ int lg_floor(double x) {
     x = x > 1073741824.0 ? 1073741824.0 : x;
     x = x < -1073741824.0 ? -1073741824.0 : x;
     return (int)__builtin_floor(x);
@@ -209,7 +222,7 @@ __device__ __forceinline__ int lg_floor(double x) {
 
 // include/extrap.h:41-44 clamp(); clampBackground (extrap.h:46-57) on a
 // (floor, floor+1) pair is this clamp applied to both members.
-__device__ __forceinline__ int clamp1(int r, int b) { return lg_med3(r, 0, b - 1); }  // b >= 1
+__host__ __device__ __forceinline__ int clamp1(int r, int b) { return lg_med3(r, 0, b - 1); }  // b >= 1
 
 // Sample position x + dt*u: computed in double (dt is a double in the
 // reference, cuda/interp.cu:36-37,68-70) and narrowed to R.
@@ -488,7 +501,7 @@ struct Splat2 {
 // kernel for the others); both are always launched and every workgroup decides by THIS function, from the matrix in
 // device memory, whether the batch item is its own (no host synchronisation).  Ai: the inverse (valid when true).
 template <typename R>
-__device__ __forceinline__ bool affine_item_regular(const R *An, double (&Ai)[9]) {
+__host__ __device__ __forceinline__ bool affine_item_regular(const R *An, double (&Ai)[9]) {
     double a[9];
 #pragma unroll
     for (int q = 0; q < 9; ++q) a[q] = (double)An[q];

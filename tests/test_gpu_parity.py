@@ -923,8 +923,9 @@ def test_persistent_x_pass_any_pair_count(ext, shape, batch, inverse):
 @pytest.mark.parametrize("kind", ["near_identity", "rotation", "zoom", "flip", "singular", "shear_far"])
 @pytest.mark.parametrize("bc", [False, True])
 def test_affine_backward_tiled_splat(ext, dtype, kind, bc):
-    """affine_interp_backward's image splat through the LDS window, several tiles per volume,
-    with maps whose image leaves the window (rotation, zoom, flip fall back to global atomics)."""
+    """affine_interp_backward's image splat, several boxes / tiles per volume: by target boxes for the regular
+    matrices (rotation, zoom, flip included: affine_splat_box_kernel), by the gated general tiled kernel for the
+    singular and the wild ones; then the tiled kernel alone and global atomics alone, all against the oracle."""
     rng = np.random.default_rng(77)
     sp, nn, nc = (36, 20, 70), 2, 2
     I = rnd(rng, ((1 if bc else nn), nc) + sp, dtype)
