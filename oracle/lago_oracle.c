@@ -41,8 +41,10 @@ int oracle_get_threads(void) { return lg_oracle_threads; }
 #define LG_FMAD(a, b, c) fma((a), (b), (c))
 #endif
 
+/* LG_WIDE: the accumulation type of the oracle_*_wide entry points (lago_oracle_impl.h: lg_acc) */
 #define REAL float
 #define SUF _f32
+#define LG_WIDE double
 #define LG_SQRT sqrtf
 #ifdef LAGO_ORACLE_STRICT
 #define LG_FMA(a, b, c) ((a) * (b) + (c))
@@ -52,11 +54,13 @@ int oracle_get_threads(void) { return lg_oracle_threads; }
 #include "lago_oracle_impl.h"
 #undef REAL
 #undef SUF
+#undef LG_WIDE
 #undef LG_SQRT
 #undef LG_FMA
 
 #define REAL double
 #define SUF _f64
+#define LG_WIDE long double   /* x86-64: 64-bit mantissa */
 #define LG_SQRT sqrt
 #ifdef LAGO_ORACLE_STRICT
 #define LG_FMA(a, b, c) ((a) * (b) + (c))
@@ -66,6 +70,7 @@ int oracle_get_threads(void) { return lg_oracle_threads; }
 #include "lago_oracle_impl.h"
 #undef REAL
 #undef SUF
+#undef LG_WIDE
 #undef LG_SQRT
 #undef LG_FMA
 

@@ -281,6 +281,70 @@ def regrid_backward(go, inshape, shape, origin, spacing):
     return d_I
 
 
+# --------------------------------------------------------------------------- wide scatter sums (tests' yardstick)
+#
+# Every scatter-add output in a second form: the same float positions, weights and masses as the entry points above (one
+# body in lago_oracle_impl.h serves both), but each contribution's product and the sum per cell taken in a wider type
+# (double for float32 inputs, x87 long double for float64 inputs, rounded to double once at the end).  Each function
+# returns (sum, sabs, count), float64 arrays of the output's shape: the sum, the sum of the absolute values of the
+# contributions and their number (zero-valued ones included).  tests/scatter_bound.py turns sabs and count into a
+# rigorous bound per cell.
+
+
+def _wide_out(shape):
+    return tuple(np.zeros(shape, dtype=np.float64) for _ in range(3))
+
+
+def interp_backward_wide(go, u, dt, broadcast_I=False):
+    """d_I of interp_backward.  broadcast_I: the image has batch 1, the batch accumulates into its one plane."""
+    go = _c(go)
+    u = _c(u, go.dtype)
+    dim, nx, ny, nz = _sp(go.shape[2:])
+    nn, nc = go.shape[0], go.shape[1]
+    out = _wide_out(((1 if broadcast_I else nn), nc) + go.shape[2:])
+    _call("oracle_interp_backward_wide", go.dtype, *[_p(a) for a in out], _p(go), _p(u), c_double(dt), c_int(dim),
+          c_long(nn), c_long(nc), c_long(nx), c_long(ny), c_long(nz), c_int(bool(broadcast_I)))
+    return out
+
+
+def interp_hessian_diagonal_image_wide(I, u, dt):
+    I = _c(I)
+    u = _c(u, I.dtype)
+    nn = max(I.shape[0], u.shape[0])
+    out = _wide_out(I.shape)
+    _call("oracle_interp_hessian_diagonal_image_wide", I.dtype, *[_p(a) for a in out], _p(u), c_double(dt),
+          c_long(I.shape[0]), c_long(nn), c_long(I.shape[1]), c_long(I.shape[2]), c_long(I.shape[3]))
+    return out
+
+
+def affine_interp_backward_wide(go, I, A, T, need_I=True, need_A=True, need_T=True):
+    """((sum, sabs, count) of d_I, of d_A, of d_T); a group that is not needed is None."""
+    I = _c(I)
+    go, A, T = _c(go, I.dtype), _c(A, I.dtype), _c(T, I.dtype)
+    dim, nx, ny, nz = _sp(I.shape[2:])
+    nn = go.shape[0]
+    bc = int(I.shape[0] == 1 and nn > 1)
+    oI = _wide_out(I.shape) if need_I else (None,) * 3
+    oA = _wide_out(A.shape) if need_A else (None,) * 3
+    oT = _wide_out(T.shape) if need_T else (None,) * 3
+    _call("oracle_affine_interp_backward_wide", I.dtype, *[_p(a) for a in oI + oA + oT], _p(go), _p(I), _p(A), _p(T),
+          c_int(dim), c_long(nn), c_long(go.shape[1]), c_long(nx), c_long(ny), c_long(nz), c_int(bc))
+    return (oI if need_I else None), (oA if need_A else None), (oT if need_T else None)
+
+
+def regrid_backward_wide(go, inshape, shape, origin, spacing):
+    go = _c(go)
+    inshape = [int(s) for s in inshape]
+    dim, nx, ny, nz = _sp(tuple(inshape))
+    shape = [int(s) for s in shape]
+    N = shape + [1] * (3 - dim)
+    out = _wide_out(go.shape[:2] + tuple(inshape))
+    _call("oracle_regrid_backward_wide", go.dtype, *[_p(a) for a in out], _p(go), c_int(dim), c_long(go.shape[0]),
+          c_long(go.shape[1]), c_long(nx), c_long(ny), c_long(nz), c_long(N[0]), c_long(N[1]), c_long(N[2]),
+          _dv(origin, dim), _dv(spacing, dim))
+    return out
+
+
 # --------------------------------------------------------------------------- FluidMetric (metric.py:37-97)
 
 

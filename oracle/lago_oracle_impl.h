@@ -142,17 +142,62 @@ static void FN(lg_trilerp_grad)(REAL *gx, REAL *gy, REAL *gz, const REAL *img, R
 
 /* ---- splat ---------------------------------------------------------------- */
 
+/* Where a splat deposits.  `plain` set: the reference's accumulation, d[at] += (dx*dy[*dz]) * mass in REAL (every
+ * oracle_* entry point).  `plain` NULL: the wide form of the oracle_*_wide entry points (tests' yardstick for scatter
+ * sums): the same REAL weights and mass, but product and sum taken in LG_WIDE (double for float, long double for
+ * double), next to the sum of the absolute values and the number of contributions per cell.  Both forms go through
+ * the one lg_splat2 / lg_splat3 body below, so positions, floor, weight flips and clamp cannot drift apart. */
+typedef struct {
+    REAL *plain;
+    LG_WIDE *sum, *sabs;
+    double *count;
+} FN(lg_acc);
+
+static inline FN(lg_acc) FN(lg_acc_plain)(REAL *d) {
+    FN(lg_acc) a = {d, NULL, NULL, NULL};
+    return a;
+}
+
+static inline FN(lg_acc) FN(lg_acc_at)(const FN(lg_acc) *a, size_t off) {
+    FN(lg_acc) b = {NULL, NULL, NULL, NULL};
+    if (a->plain) {
+        b.plain = a->plain + off;
+    } else {
+        b.sum = a->sum + off;
+        b.sabs = a->sabs + off;
+        b.count = a->count + off;
+    }
+    return b;
+}
+
+/* one contribution into cell `at`: (product of the nw weights) * *mass, or, with mass NULL, the square of that product
+ * (the hessian diagonal) */
+static inline void FN(lg_acc_add)(const FN(lg_acc) *a, size_t at, const REAL *w, int nw, const REAL *mass) {
+    if (a->plain) {
+        REAL ww = w[0];
+        for (int q = 1; q < nw; ++q) ww = ww * w[q];
+        a->plain[at] += ww * (mass ? *mass : ww);
+    } else {
+        LG_WIDE t = (LG_WIDE)w[0];
+        for (int q = 1; q < nw; ++q) t *= (LG_WIDE)w[q];
+        t *= mass ? (LG_WIDE)*mass : t;
+        a->sum[at] += t;
+        a->sabs[at] += t < 0 ? -t : t;
+        a->count[at] += 1.0;
+    }
+}
+
 /* include/interp.h:403-425 atomicSplat 2D + :330-363 splat_neighbor.  The
  * weight flips (dy = 1-dy, dx = 1-dx) are sequential, exactly as written. */
-static void FN(lg_splat2)(REAL *d, REAL mass, REAL x, REAL y, long w, long h) {
+static inline void FN(lg_splat2)(const FN(lg_acc) *d, REAL mass, REAL x, REAL y, long w, long h) {
     int xi0 = FN(lg_floor)(x), yi0 = FN(lg_floor)(y);
     REAL dx = (REAL)1.f - (x - (REAL)xi0);
     REAL dy = (REAL)1.f - (y - (REAL)yi0);
     for (int xi = xi0; xi < xi0 + 2; xi++) {
         for (int yi = yi0; yi < yi0 + 2; yi++) {
             int i = FN(lg_clamp)(xi, w), j = FN(lg_clamp)(yi, h);
-            REAL ww = dx * dy;
-            d[(size_t)i * h + j] += ww * mass;
+            const REAL ws[2] = {dx, dy};
+            FN(lg_acc_add)(d, (size_t)i * h + j, ws, 2, &mass);
             dy = (REAL)1.f - dy;
         }
         dx = (REAL)1.f - dx;
@@ -160,7 +205,7 @@ static void FN(lg_splat2)(REAL *d, REAL mass, REAL x, REAL y, long w, long h) {
 }
 
 /* include/interp.h:426-454 atomicSplat 3D + :365-401 */
-static void FN(lg_splat3)(REAL *d, REAL mass, REAL x, REAL y, REAL z, long w, long h, long l) {
+static inline void FN(lg_splat3)(const FN(lg_acc) *d, REAL mass, REAL x, REAL y, REAL z, long w, long h, long l) {
     int xi0 = FN(lg_floor)(x), yi0 = FN(lg_floor)(y), zi0 = FN(lg_floor)(z);
     REAL dx = (REAL)1.f - (x - (REAL)xi0);
     REAL dy = (REAL)1.f - (y - (REAL)yi0);
@@ -169,14 +214,40 @@ static void FN(lg_splat3)(REAL *d, REAL mass, REAL x, REAL y, REAL z, long w, lo
         for (int yi = yi0; yi < yi0 + 2; yi++) {
             for (int zi = zi0; zi < zi0 + 2; zi++) {
                 int i = FN(lg_clamp)(xi, w), j = FN(lg_clamp)(yi, h), k = FN(lg_clamp)(zi, l);
-                REAL ww = dx * dy * dz;
-                d[((size_t)i * h + j) * l + k] += ww * mass;
+                const REAL ws[3] = {dx, dy, dz};
+                FN(lg_acc_add)(d, ((size_t)i * h + j) * l + k, ws, 3, &mass);
                 dz = (REAL)1.f - dz;
             }
             dy = (REAL)1.f - dy;
         }
         dx = (REAL)1.f - dx;
     }
+}
+
+/* The buffers of a wide accumulation over `n` cells (zeroed), and their narrowing to the caller's three double arrays
+ * (one rounding of the sums at the very end). */
+static int FN(lg_acc_wide_alloc)(FN(lg_acc) *a, double *count, size_t n) {
+    a->plain = NULL;
+    a->sum = (LG_WIDE *)calloc(n ? n : 1, sizeof(LG_WIDE));
+    a->sabs = (LG_WIDE *)calloc(n ? n : 1, sizeof(LG_WIDE));
+    a->count = count;
+    if (!a->sum || !a->sabs) {
+        free(a->sum);
+        free(a->sabs);
+        return -2;
+    }
+    for (size_t q = 0; q < n; ++q) count[q] = 0.0;
+    return 0;
+}
+
+static void FN(lg_acc_wide_finish)(FN(lg_acc) *a, double *sum, double *sabs, size_t n) {
+    for (size_t q = 0; q < n; ++q) {
+        sum[q] = (double)a->sum[q];
+        sabs[q] = (double)a->sabs[q];
+    }
+    free(a->sum);
+    free(a->sabs);
+    a->sum = a->sabs = NULL;
 }
 
 /* The interpolation cores at caller-given points (test hook: pinned value by value against the
@@ -280,8 +351,8 @@ int FN(oracle_interp_forward)(REAL *out, const REAL *I, const REAL *u, double dt
 }
 
 /* One x-slab [i0, i1) of one channel of one batch item of interp_kernel_backward_{2,3}d (cuda/interp.cu:132-244):
- * the splat goes into `dIc` (a full channel plane), d_u is owned voxel by voxel. */
-static void FN(lg_interp_backward_slab)(REAL *dIc, REAL *dun, const REAL *gc, const REAL *Ic, const REAL *un,
+ * the splat goes into `dIc` (a full channel plane, plain or wide), d_u is owned voxel by voxel. */
+static void FN(lg_interp_backward_slab)(const FN(lg_acc) *dIc, REAL *dun, const REAL *gc, const REAL *Ic, const REAL *un,
                                         double dt, int dim, long nx, long ny, long nz, long i0, long i1, int need_I,
                                         int need_u) {
     const size_t nvox = (size_t)nx * ny * nz;
@@ -345,7 +416,8 @@ int FN(oracle_interp_backward)(REAL *d_I, REAL *d_u, const REAL *go, const REAL 
                 const long n = t / slabs, sl = t % slabs;
                 const long i0 = nx * sl / slabs, i1 = nx * (sl + 1) / slabs;
                 const REAL *In = broadcast_I ? I : I + (size_t)n * nc * nvox;
-                FN(lg_interp_backward_slab)(priv + (size_t)t * nvox, d_u + (size_t)n * dim * nvox,
+                const FN(lg_acc) acc = FN(lg_acc_plain)(priv + (size_t)t * nvox);
+                FN(lg_interp_backward_slab)(&acc, d_u + (size_t)n * dim * nvox,
                                             go + ((size_t)n * nc + c) * nvox, In + (size_t)c * nvox,
                                             u + (size_t)n * dim * nvox, dt, dim, nx, ny, nz, i0, i1, need_I, need_u);
             }
@@ -368,20 +440,44 @@ int FN(oracle_interp_backward)(REAL *d_I, REAL *d_u, const REAL *go, const REAL 
         const REAL *In = broadcast_I ? I : I + (size_t)n * nc * nvox;
         REAL *dIn = broadcast_I ? d_I : d_I + (size_t)n * nc * nvox;
         const REAL *gon = go + (size_t)n * nc * nvox;
-        for (long c = 0; c < nc; ++c)
-            FN(lg_interp_backward_slab)(dIn + (size_t)c * nvox, dun, gon + (size_t)c * nvox, In + (size_t)c * nvox, un,
+        for (long c = 0; c < nc; ++c) {
+            const FN(lg_acc) acc = FN(lg_acc_plain)(dIn + (size_t)c * nvox);
+            FN(lg_interp_backward_slab)(&acc, dun, gon + (size_t)c * nvox, In + (size_t)c * nvox, un,
                                         dt, dim, nx, ny, nz, 0, nx, need_I, need_u);
+        }
     }
+    return 0;
+}
+
+/* d_I of oracle_interp_backward in the wide form (see lg_acc): sum, sabs, count of the shape of d_I, as double.
+ * Positions, weights and clamp are lg_interp_backward_slab's; a broadcast image accumulates over the batch into the
+ * one plane.  Planes that no other batch item touches may run in parallel (the bits do not depend on it). */
+int FN(oracle_interp_backward_wide)(double *sum, double *sabs, double *count, const REAL *go, const REAL *u, double dt,
+                                    int dim, long nn, long nc, long nx, long ny, long nz, int broadcast_I) {
+    if (dim != 2 && dim != 3) return -1;
+    if (dim == 2) nz = 1;
+    const size_t nvox = (size_t)nx * ny * nz;
+    const size_t nI = (broadcast_I ? 1 : (size_t)nn) * nc * nvox;
+    FN(lg_acc) acc;
+    if (FN(lg_acc_wide_alloc)(&acc, count, nI)) return -2;
+    LG_PARALLEL_FOR_IF(!broadcast_I)
+    for (long n = 0; n < nn; ++n)
+        for (long c = 0; c < nc; ++c) {
+            const FN(lg_acc) pl = FN(lg_acc_at)(&acc, ((broadcast_I ? 0 : (size_t)n * nc) + c) * nvox);
+            FN(lg_interp_backward_slab)(&pl, NULL, go + ((size_t)n * nc + c) * nvox, NULL, u + (size_t)n * dim * nvox, dt,
+                                        dim, nx, ny, nz, 0, nx, 1, 0);
+        }
+    FN(lg_acc_wide_finish)(&acc, sum, sabs, nI);
     return 0;
 }
 
 /* cuda/interp.cu:317-381 + include/interp.h:459-544.  2D only.  The kernel
  * passes `out` (not the per-channel pointer) to the point routine, so every
- * (n, c) accumulates into plane 0 of the output; restated as coded. */
-int FN(oracle_interp_hessian_diagonal_image)(REAL *out, const REAL *u, double dt, long nI, long nn, long nc,
-                                             long nx, long ny) {
+ * (n, c) accumulates into plane 0 of the output; restated as coded.  A term is
+ * w * w with w = omt * omu etc. rounded to REAL (plain) or both products wide. */
+static void FN(lg_hessian_diagonal_body)(const FN(lg_acc) *out, const REAL *u, double dt, long nn, long nc, long nx,
+                                         long ny) {
     const size_t nxy = (size_t)nx * ny;
-    memset(out, 0, (size_t)nI * nc * nxy * sizeof(REAL));
     for (long n = 0; n < nn; ++n) {
         const REAL *un = u + (size_t)n * 2 * nxy;
         for (long i = 0; i < nx; ++i)
@@ -395,15 +491,34 @@ int FN(oracle_interp_hessian_diagonal_image)(REAL *out, const REAL *u, double dt
                 REAL omt = (REAL)1.f - t, omu = (REAL)1.f - uu;
                 FN(lg_clamp_pair)(&fx, &cx, nx);
                 FN(lg_clamp_pair)(&fy, &cy, ny);
-                REAL w0 = omt * omu, w1 = t * omu, w2 = t * uu, w3 = omt * uu;
-                for (long c = 0; c < nc; ++c) {
-                    out[(size_t)fx * ny + fy] += w0 * w0;
-                    out[(size_t)cx * ny + fy] += w1 * w1;
-                    out[(size_t)cx * ny + cy] += w2 * w2;
-                    out[(size_t)fx * ny + cy] += w3 * w3;
-                }
+                const size_t at[4] = {(size_t)fx * ny + fy, (size_t)cx * ny + fy, (size_t)cx * ny + cy, (size_t)fx * ny + cy};
+                const REAL wa[4] = {omt, t, t, omt}, wb[4] = {omu, omu, uu, uu};
+                for (long c = 0; c < nc; ++c)
+                    for (int q = 0; q < 4; ++q) {
+                        const REAL ws[2] = {wa[q], wb[q]};
+                        FN(lg_acc_add)(out, at[q], ws, 2, NULL);
+                    }
             }
     }
+}
+
+int FN(oracle_interp_hessian_diagonal_image)(REAL *out, const REAL *u, double dt, long nI, long nn, long nc,
+                                             long nx, long ny) {
+    const size_t nxy = (size_t)nx * ny;
+    memset(out, 0, (size_t)nI * nc * nxy * sizeof(REAL));
+    const FN(lg_acc) acc = FN(lg_acc_plain)(out);
+    FN(lg_hessian_diagonal_body)(&acc, u, dt, nn, nc, nx, ny);
+    return 0;
+}
+
+/* the wide form: sum, sabs, count of the shape of the output (every plane but the first stays empty) */
+int FN(oracle_interp_hessian_diagonal_image_wide)(double *sum, double *sabs, double *count, const REAL *u, double dt,
+                                                  long nI, long nn, long nc, long nx, long ny) {
+    const size_t ntot = (size_t)nI * nc * nx * ny;
+    FN(lg_acc) acc;
+    if (FN(lg_acc_wide_alloc)(&acc, count, ntot)) return -2;
+    FN(lg_hessian_diagonal_body)(&acc, u, dt, nn, nc, nx, ny);
+    FN(lg_acc_wide_finish)(&acc, sum, sabs, ntot);
     return 0;
 }
 
@@ -820,6 +935,26 @@ int FN(oracle_affine_interp_forward_cpuref)(REAL *out, const REAL *I, const REAL
     return 0;
 }
 
+/* One voxel of affine_interp_kernel_backward_{2,3}d (cuda/affine.cu:171-536): its position, the splat of `diff` into
+ * dIn (when given, plain or wide) and the gradient of In at the position (when g is given).  Shared by the plain and
+ * the wide entry point. */
+static inline void FN(lg_affine_backward_voxel)(const FN(lg_acc) *dIn, REAL *g, const REAL *In, const REAL *An,
+                                                const REAL *Tn, int dim, REAL diff, REAL fi, REAL fj, REAL fk, REAL ox,
+                                                REAL oy, REAL oz, long nx, long ny, long nz) {
+    if (dim == 2) {
+        REAL hx = LG_FMA(An[0], fi, An[1] * fj) + Tn[0] + ox;
+        REAL hy = LG_FMA(An[2], fi, An[3] * fj) + Tn[1] + oy;
+        if (dIn) FN(lg_splat2)(dIn, diff, hx, hy, nx, ny);
+        if (g) FN(lg_bilerp_grad)(&g[0], &g[1], In, hx, hy, nx, ny);
+    } else {
+        REAL hx = LG_FMA(An[2], fk, LG_FMA(An[0], fi, An[1] * fj)) + Tn[0] + ox;
+        REAL hy = LG_FMA(An[5], fk, LG_FMA(An[3], fi, An[4] * fj)) + Tn[1] + oy;
+        REAL hz = LG_FMA(An[8], fk, LG_FMA(An[6], fi, An[7] * fj)) + Tn[2] + oz;
+        if (dIn) FN(lg_splat3)(dIn, diff, hx, hy, hz, nx, ny, nz);
+        if (g) FN(lg_trilerp_grad)(&g[0], &g[1], &g[2], In, hx, hy, hz, nx, ny, nz);
+    }
+}
+
 /* cuda/affine.cu:171-536 (kernels), :538-610 (host).  One 16x32 block per
  * (n, c): thread (ii, jj) accumulates voxels i = ii (mod 16), j = jj (mod 32),
  * all k, then the 512 partials are tree-reduced (256, 128, ... 1).  That order
@@ -847,7 +982,8 @@ int FN(oracle_affine_interp_backward)(REAL *d_I, REAL *d_A, REAL *d_T, const REA
         for (long c = 0; c < nc; ++c) {
             const REAL *gon = go + ((size_t)n * nc + c) * nvox;
             const REAL *In = I + ((broadcast_I ? 0 : (size_t)n * nc) + c) * nvox;
-            REAL *dIn = need_I ? d_I + ((broadcast_I ? 0 : (size_t)n * nc) + c) * nvox : NULL;
+            const FN(lg_acc) dIn = FN(lg_acc_plain)(need_I ? d_I + ((broadcast_I ? 0 : (size_t)n * nc) + c) * nvox : NULL);
+            const int need_g = need_A || need_T;
             for (int ii = 0; ii < TX; ++ii)
                 for (int jj = 0; jj < TY; ++jj) {
                     REAL *p = part[ii * TY + jj];
@@ -859,22 +995,12 @@ int FN(oracle_affine_interp_backward)(REAL *d_I, REAL *d_A, REAL *d_T, const REA
                             for (long k = 0; k < nz; ++k) {
                                 size_t ix = ((size_t)i * ny + j) * nz + k;
                                 REAL diff = gon[ix];
-                                REAL gx, gy, gz = 0, fk = 0;
-                                if (dim == 2) {
-                                    REAL hx = LG_FMA(An[0], fi, An[1] * fj) + Tn[0] + ox;
-                                    REAL hy = LG_FMA(An[2], fi, An[3] * fj) + Tn[1] + oy;
-                                    if (need_I) FN(lg_splat2)(dIn, diff, hx, hy, nx, ny);
-                                    if (!(need_A || need_T)) continue;
-                                    FN(lg_bilerp_grad)(&gx, &gy, In, hx, hy, nx, ny);
-                                } else {
-                                    fk = (REAL)k - oz;
-                                    REAL hx = LG_FMA(An[2], fk, LG_FMA(An[0], fi, An[1] * fj)) + Tn[0] + ox;
-                                    REAL hy = LG_FMA(An[5], fk, LG_FMA(An[3], fi, An[4] * fj)) + Tn[1] + oy;
-                                    REAL hz = LG_FMA(An[8], fk, LG_FMA(An[6], fi, An[7] * fj)) + Tn[2] + oz;
-                                    if (need_I) FN(lg_splat3)(dIn, diff, hx, hy, hz, nx, ny, nz);
-                                    if (!(need_A || need_T)) continue;
-                                    FN(lg_trilerp_grad)(&gx, &gy, &gz, In, hx, hy, hz, nx, ny, nz);
-                                }
+                                REAL g[3] = {0, 0, 0};
+                                REAL fk = dim == 3 ? (REAL)k - oz : 0;
+                                FN(lg_affine_backward_voxel)(need_I ? &dIn : NULL, need_g ? g : NULL, In, An, Tn, dim, diff,
+                                                             fi, fj, fk, ox, oy, oz, nx, ny, nz);
+                                if (!need_g) continue;
+                                REAL gx = g[0], gy = g[1], gz = g[2];
                                 gx *= diff;
                                 gy *= diff;
                                 gz *= diff;
@@ -908,6 +1034,80 @@ int FN(oracle_affine_interp_backward)(REAL *d_I, REAL *d_A, REAL *d_T, const REA
         }
     }
     free(part);
+    return 0;
+}
+
+/* The wide form of oracle_affine_interp_backward (see lg_acc).  I_* (shape of d_I): the splat.  A_* (nn, dim, dim) and
+ * T_* (nn, dim): the terms g_a * diff * f_b and g_a * diff, with the gradient g from lg_*lerp_grad in REAL as in the
+ * plain form, product and sum in LG_WIDE.  Any of the three groups may be NULL; I may be NULL when neither A_ nor T_
+ * is asked for.  (These twelve sums per item cannot go through lg_acc_add: the plain form keeps them in 512 partials
+ * that it tree-reduces, an order that is part of what it restates; what the two forms share is lg_affine_backward_voxel,
+ * i.e. position, splat and gradient -- the factors g, diff, f of a term -- and only the two multiplications differ.) */
+int FN(oracle_affine_interp_backward_wide)(double *I_sum, double *I_sabs, double *I_count, double *A_sum, double *A_sabs,
+                                           double *A_count, double *T_sum, double *T_sabs, double *T_count,
+                                           const REAL *go, const REAL *I, const REAL *A, const REAL *T, int dim, long nn,
+                                           long nc, long nx, long ny, long nz, int broadcast_I) {
+    if (dim != 2 && dim != 3) return -1;
+    if (dim == 2) nz = 1;
+    const size_t nvox = (size_t)nx * ny * nz;
+    const size_t nI = (broadcast_I ? 1 : (size_t)nn) * nc * nvox;
+    const int need_I = I_sum != NULL, need_A = A_sum != NULL, need_T = T_sum != NULL;
+    const int need_g = need_A || need_T;
+    if (need_g && !I) return -1;
+    const REAL ox = (REAL)(.5 * (double)(REAL)(nx - 1));
+    const REAL oy = (REAL)(.5 * (double)(REAL)(ny - 1));
+    const REAL oz = (REAL)(.5 * (double)(REAL)(nz - 1));
+    FN(lg_acc) acc = {NULL, NULL, NULL, NULL};
+    if (need_I && FN(lg_acc_wide_alloc)(&acc, I_count, nI)) return -2;
+    for (long n = 0; n < nn; ++n) {
+        const REAL *An = A + (size_t)n * dim * dim;
+        const REAL *Tn = T + (size_t)n * dim;
+        LG_WIDE ws[12], wa[12];
+        for (int q = 0; q < 12; ++q) ws[q] = wa[q] = 0;
+        for (long c = 0; c < nc; ++c) {
+            const REAL *gon = go + ((size_t)n * nc + c) * nvox;
+            const REAL *In = need_g ? I + ((broadcast_I ? 0 : (size_t)n * nc) + c) * nvox : NULL;
+            FN(lg_acc) dIn = acc;
+            if (need_I) dIn = FN(lg_acc_at)(&acc, ((broadcast_I ? 0 : (size_t)n * nc) + c) * nvox);
+            for (long i = 0; i < nx; ++i) {
+                REAL fi = (REAL)i - ox;
+                for (long j = 0; j < ny; ++j) {
+                    REAL fj = (REAL)j - oy;
+                    for (long k = 0; k < nz; ++k) {
+                        size_t ix = ((size_t)i * ny + j) * nz + k;
+                        REAL diff = gon[ix];
+                        REAL g[3] = {0, 0, 0};
+                        REAL fk = dim == 3 ? (REAL)k - oz : 0;
+                        FN(lg_affine_backward_voxel)(need_I ? &dIn : NULL, need_g ? g : NULL, In, An, Tn, dim, diff, fi, fj,
+                                                     fk, ox, oy, oz, nx, ny, nz);
+                        if (!need_g) continue;
+                        const REAL f[3] = {fi, fj, fk};
+                        for (int a = 0; a < dim; ++a) {
+                            const LG_WIDE gd = (LG_WIDE)g[a] * (LG_WIDE)diff;
+                            ws[9 + a] += gd;
+                            wa[9 + a] += gd < 0 ? -gd : gd;
+                            for (int b = 0; b < dim; ++b) {
+                                const LG_WIDE t = gd * (LG_WIDE)f[b];
+                                ws[a * dim + b] += t;
+                                wa[a * dim + b] += t < 0 ? -t : t;
+                            }
+                        }
+                    }
+                }
+            }
+        }
+        for (int q = 0; need_A && q < dim * dim; ++q) {
+            A_sum[(size_t)n * dim * dim + q] = (double)ws[q];
+            A_sabs[(size_t)n * dim * dim + q] = (double)wa[q];
+            A_count[(size_t)n * dim * dim + q] = (double)nc * (double)nvox;
+        }
+        for (int q = 0; need_T && q < dim; ++q) {
+            T_sum[(size_t)n * dim + q] = (double)ws[9 + q];
+            T_sabs[(size_t)n * dim + q] = (double)wa[9 + q];
+            T_count[(size_t)n * dim + q] = (double)nc * (double)nvox;
+        }
+    }
+    if (need_I) FN(lg_acc_wide_finish)(&acc, I_sum, I_sabs, nI);
     return 0;
 }
 
@@ -949,35 +1149,55 @@ int FN(oracle_regrid_forward)(REAL *out, const REAL *I, int dim, long nn, long n
 }
 
 /* cuda/affine.cu:736-800 (kernels), :802-855 (host).  Here hz = (k-oz)*Sz+Oz
- * per voxel (affine.cu:791), not the running sum of the forward. */
-int FN(oracle_regrid_backward)(REAL *d_I, const REAL *go, int dim, long nn, long nc, long nx, long ny, long nz,
-                               long Nx, long Ny, long Nz, const double *origin, const double *spacing) {
-    if (dim != 2 && dim != 3) return -1;
-    if (dim == 2) { nz = 1; Nz = 1; }
+ * per voxel (affine.cu:791), not the running sum of the forward.  One body for the plain and the wide form. */
+static void FN(lg_regrid_backward_body)(const FN(lg_acc) *d_I, const REAL *go, int dim, long nn, long nc, long nx,
+                                        long ny, long nz, long Nx, long Ny, long Nz, const double *origin,
+                                        const double *spacing) {
     const size_t nvox = (size_t)nx * ny * nz, Nvox = (size_t)Nx * Ny * Nz;
     const REAL Ox = (REAL)origin[0], Oy = (REAL)origin[1], Oz = dim == 3 ? (REAL)origin[2] : 0;
     const REAL Sx = (REAL)spacing[0], Sy = (REAL)spacing[1], Sz = dim == 3 ? (REAL)spacing[2] : 0;
     const REAL ox = (REAL)(.5 * (double)(REAL)(Nx - 1));
     const REAL oy = (REAL)(.5 * (double)(REAL)(Ny - 1));
     const REAL oz = (REAL)(.5 * (double)(REAL)(Nz - 1));
-    memset(d_I, 0, (size_t)nn * nc * nvox * sizeof(REAL));
     for (long q = 0; q < nn * nc; ++q) {
-        REAL *dIn = d_I + (size_t)q * nvox;
+        const FN(lg_acc) dIn = FN(lg_acc_at)(d_I, (size_t)q * nvox);
         const REAL *gon = go + (size_t)q * Nvox;
         for (long i = 0; i < Nx; ++i)
             for (long j = 0; j < Ny; ++j) {
                 REAL hx = LG_FMA((REAL)i - ox, Sx, Ox);
                 REAL hy = LG_FMA((REAL)j - oy, Sy, Oy);
                 if (dim == 2) {
-                    FN(lg_splat2)(dIn, gon[(size_t)i * Ny + j], hx, hy, nx, ny);
+                    FN(lg_splat2)(&dIn, gon[(size_t)i * Ny + j], hx, hy, nx, ny);
                 } else {
                     for (long k = 0; k < Nz; ++k) {
                         REAL hz = LG_FMA((REAL)k - oz, Sz, Oz);
-                        FN(lg_splat3)(dIn, gon[((size_t)i * Ny + j) * Nz + k], hx, hy, hz, nx, ny, nz);
+                        FN(lg_splat3)(&dIn, gon[((size_t)i * Ny + j) * Nz + k], hx, hy, hz, nx, ny, nz);
                     }
                 }
             }
     }
+}
+
+int FN(oracle_regrid_backward)(REAL *d_I, const REAL *go, int dim, long nn, long nc, long nx, long ny, long nz,
+                               long Nx, long Ny, long Nz, const double *origin, const double *spacing) {
+    if (dim != 2 && dim != 3) return -1;
+    if (dim == 2) { nz = 1; Nz = 1; }
+    memset(d_I, 0, (size_t)nn * nc * nx * ny * nz * sizeof(REAL));
+    const FN(lg_acc) acc = FN(lg_acc_plain)(d_I);
+    FN(lg_regrid_backward_body)(&acc, go, dim, nn, nc, nx, ny, nz, Nx, Ny, Nz, origin, spacing);
+    return 0;
+}
+
+int FN(oracle_regrid_backward_wide)(double *sum, double *sabs, double *count, const REAL *go, int dim, long nn, long nc,
+                                    long nx, long ny, long nz, long Nx, long Ny, long Nz, const double *origin,
+                                    const double *spacing) {
+    if (dim != 2 && dim != 3) return -1;
+    if (dim == 2) { nz = 1; Nz = 1; }
+    const size_t ntot = (size_t)nn * nc * nx * ny * nz;
+    FN(lg_acc) acc;
+    if (FN(lg_acc_wide_alloc)(&acc, count, ntot)) return -2;
+    FN(lg_regrid_backward_body)(&acc, go, dim, nn, nc, nx, ny, nz, Nx, Ny, Nz, origin, spacing);
+    FN(lg_acc_wide_finish)(&acc, sum, sabs, ntot);
     return 0;
 }
 
