@@ -247,7 +247,32 @@ long long lago_reversed_launches(void);
      * pass without atomics: every element of d_u is written once, identically from run to run.  No counterpart in  \
      * the reference. */                                                                                            \
     int lago_jacdet_backward##SUF(REAL *d_u, const REAL *grad_out, const REAL *u, int displacement, int dim,        \
-                                  int64_t nn, int64_t nx, int64_t ny, int64_t nz, void *stream);
+                                  int64_t nn, int64_t nx, int64_t ny, int64_t nz, void *stream);                    \
+    /* invert_displacement: `iters` steps of the fixed-point iteration for the inverse of x -> x + u(x),            \
+     *   v_0 = -u,  v_{k+1}(x) = -u(x + v_k(x))                                                                     \
+     * (multilinear interpolation of u with the clamped border of lago_interp_forward), all steps in one kernel:     \
+     * v stays in registers and is written once.  u, out: (nn, dim, sp).  Bit for bit the value of                  \
+     *   v = -u; repeat iters times: v = -lago_interp_forward(I = u, u = v, dt = 1)                                 \
+     * The only early stop: a wavefront whose step changed no bit of v ends its loop (later steps would reproduce   \
+     * the same bits).  The iteration converges where the interpolated u is a contraction (Lipschitz constant < 1). \
+     * LAGO_ERR_INVALID for iters < 0, dim not in {2, 3} and out overlapping u; nn == 0 does nothing.  No            \
+     * counterpart in the reference. */                                                                             \
+    int lago_invert_disp_forward##SUF(REAL *out, const REAL *u, int iters, int dim, int64_t nn, int64_t nx,         \
+                                      int64_t ny, int64_t nz, void *stream);                                        \
+    /* the adjoint solve of the CONVERGED inverse (not of the truncated iteration): with psi = id + v and            \
+     * G[c][a] = (d_a u_c)(psi(x)) (the gradient of the interpolant, as lago_interp_backward's d_u forms it),        \
+     * M = I + G (the 1 added to the rounded gradient), lam = -(M^-T) grad_out by the adjugate.  d_u of the inverse  \
+     * is the splat of lam at psi: lago_interp_backward(d_I, ., grad_out = lam, I = u, u = v, dt = 1, need_I).       \
+     * grad_out, u, v, lam: (nn, dim, sp).  Every product, sum and quotient is rounded on its own, in this order:    \
+     *   2D: det = M00*M11 - M01*M10                                                                                \
+     *       lam0 = -((M11*g0 - M10*g1) / det)   lam1 = -((M00*g1 - M01*g0) / det)                                  \
+     *   3D: det = (M00*(M11*M22 - M12*M21) - M01*(M10*M22 - M12*M20)) + M02*(M10*M21 - M11*M20)                    \
+     *       C[c][a] = M[c+1][a+1]*M[c+2][a+2] - M[c+1][a+2]*M[c+2][a+1]   (indices mod 3)                          \
+     *       lam_c = -(((C[c][0]*g0 + C[c][1]*g1) + C[c][2]*g2) / det)                                              \
+     * det is not guarded: where the deformation folds (det M <= 0 or tiny) the IEEE result stands.  One gather     \
+     * pass, no atomics, nothing cleared: identical from call to call.  lam must not overlap an input. */           \
+    int lago_invert_disp_adjoint##SUF(REAL *lam, const REAL *grad_out, const REAL *u, const REAL *v, int dim,       \
+                                      int64_t nn, int64_t nx, int64_t ny, int64_t nz, void *stream);
 
 LAGO_DECLARE(float, _f32)
 LAGO_DECLARE(double, _f64)

@@ -14,8 +14,8 @@ if not _BUILDING:
     from .affine import (AffineInterp, AffineInterpFunction, RegridFunction, RegridModule, StandardizedDataset,  # noqa: F401
                          affine_atlas, affine_interp, batch_average, load_affine_atlas, save_affine_atlas,
                          affine_inverse, det_2x2, invert_2x2, invert_3x3, regrid, rigid_inverse, rotation_exp_map)
-    from .deform import (InterpFunction, compose, compose_disp_vel, compose_vel_disp, identity, interp,  # noqa: F401
-                         interp_hessian_diagonal_image)
+    from .deform import (InterpFunction, InvertDisplacementFunction, compose, compose_disp_vel,  # noqa: F401
+                         compose_vel_disp, identity, interp, interp_hessian_diagonal_image, invert_displacement)
     from .diff import (JacobianDeterminantFunction, JacobianTimesVectorFieldAdjointFunction,  # noqa: F401
                        JacobianTimesVectorFieldFunction, jacobian_determinant, jacobian_times_vectorfield,
                        jacobian_times_vectorfield_adjoint)

@@ -6,6 +6,7 @@ arguments and semantics); the heavy lifting is ``lagomorph_ext.interp_*``
 """
 import numpy as np
 import torch
+from torch.autograd.function import once_differentiable
 
 from . import lagomorph_ext
 
@@ -90,3 +91,40 @@ def compose_disp_vel(u, v, dt=1.0):
 def compose_vel_disp(v, u, dt=1.0):
     """u(x) + dt*v(x + u(x))   (deform.py:65-70)"""
     return compose(u, v, ds=1.0, dt=dt)
+
+
+class InvertDisplacementFunction(torch.autograd.Function):
+    """The fixed-point inverse of id + u as ONE kernel each way (csrc/invert.hip).  Backward: the per-voxel adjoint
+    solve lam = -(I + (Du) o psi)^-T grad, psi = id + v, then the splat of lam at psi (interp_backward's d_I).  That is
+    the gradient of the CONVERGED inverse (implicit function theorem), not of the truncated iteration: no step is
+    unrolled through autograd and no intermediate field is kept.  Not in the reference."""
+
+    @staticmethod
+    def forward(ctx, u, iters):
+        v = lagomorph_ext.invert_displacement_forward(u, iters)
+        ctx.save_for_backward(u, v)
+        return v
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gradout):
+        u, v = ctx.saved_tensors
+        u = u.contiguous()
+        lam = lagomorph_ext.invert_displacement_adjoint(gradout, u, v)
+        d_u, _ = lagomorph_ext.interp_backward(lam, u, v, 1.0, True, False)
+        return d_u, None
+
+
+def invert_displacement(u, iters=20):
+    """The displacement v of the inverse of x -> x + u(x): (id + u) o (id + v) = id, by `iters` steps of the
+    fixed-point rule
+
+        v_0 = -u,    v_{k+1}(x) = -u(x + v_k(x))
+
+    with u interpolated multilinearly (clamped at the border, as interp does).  u: (N, d, *sp), d = len(sp) in {2, 3}.
+    The rule converges where the interpolated field is a contraction, i.e. its Lipschitz constant is below 1 (no
+    difference of u between neighbouring voxels as large as the voxel spacing, roughly); the error then shrinks by
+    that constant per step.  `compose(v, u)` is the residual (id + u) o (id + v) - id, zero for the exact inverse.
+    The result is bit for bit `v = -u; for k in range(iters): v = -interp(u, v)`; its gradient is that of the
+    converged inverse (InvertDisplacementFunction), exact once the iteration has reached its fixed point."""
+    return InvertDisplacementFunction.apply(u, iters)

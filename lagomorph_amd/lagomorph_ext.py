@@ -71,6 +71,8 @@ _SIGS = {
     "lago_ad_star": [_vp, _vp, _vp, _int, _i64, _i64, _i64, _i64, _vp],
     "lago_jacdet_forward": [_vp, _vp, _int, _int, _i64, _i64, _i64, _i64, _vp],
     "lago_jacdet_backward": [_vp, _vp, _vp, _int, _int, _i64, _i64, _i64, _i64, _vp],
+    "lago_invert_disp_forward": [_vp, _vp, _int, _int, _i64, _i64, _i64, _i64, _vp],
+    "lago_invert_disp_adjoint": [_vp, _vp, _vp, _vp, _int, _i64, _i64, _i64, _i64, _vp],
     "lago_fluid_metric": [_vp, _vp, _vp, _i64, _int, _vp, _vp, _vp, _vp, _vp, _vp, _dbl, _dbl, _dbl, _int, _i64, _i64,
                           _i64, _i64, _vp],
     "lago_fluid_metric_scaled": [_vp, _vp, _vp, _i64, _int, _vp, _vp, _vp, _vp, _vp, _vp, _dbl, _dbl, _dbl, _int, _i64,
@@ -476,6 +478,49 @@ def jacobian_determinant_backward(grad_out, u, displacement):
     _call("lago_jacdet_backward", u, _ptr(d_u), _ptr(grad_out), _ptr(u), int(bool(displacement)), dim, u.size(0), nx,
           ny, nz)
     return d_u
+
+
+def _check_invert(u, name="u"):
+    if not isinstance(u, torch.Tensor):
+        raise TypeError(f"{name} must be a torch.Tensor")
+    _suffix(u)
+    dim, nx, ny, nz = _spatial(u)
+    if dim not in (2, 3):
+        raise RuntimeError("Only two- and three-dimensional displacement inversion is supported")
+    if u.size(1) != dim:
+        raise RuntimeError(f"invert_displacement: {name} must be a vector field (N, d, *spatial) with d = len(spatial), "
+                           f"got {tuple(u.shape)}")
+    if not u.is_cuda:
+        raise RuntimeError(f"{name} must be a CUDA tensor")
+    return dim, nx, ny, nz
+
+
+def invert_displacement_forward(u, iters):
+    """`iters` steps of v_0 = -u, v_{k+1}(x) = -u(x + v_k(x)) in one kernel (csrc/invert.hip: invert_disp_kernel); the
+    bits of `v = -u; for k in range(iters): v = -interp_forward(u, v, 1.0)`.  Not in the reference."""
+    iters = int(iters)
+    if iters < 0:
+        raise RuntimeError(f"invert_displacement: iters must not be negative (got {iters})")
+    dim, nx, ny, nz = _check_invert(u)
+    u = u.contiguous()
+    out = torch.empty_like(u)
+    _call("lago_invert_disp_forward", u, _ptr(out), _ptr(u), iters, dim, u.size(0), nx, ny, nz)
+    return out
+
+
+def invert_displacement_adjoint(grad_out, u, v):
+    """lam = -(I + (Du)(x + v))^-T grad_out per voxel (csrc/invert.hip: invert_disp_adjoint_kernel): the adjoint solve of
+    the converged inverse v of u; d_u is interp_backward(lam, u, v, 1.0, True, False)[0].  One gather pass, no atomics."""
+    dim, nx, ny, nz = _check_invert(u)
+    for x, nm in ((grad_out, "grad_out"), (v, "v")):
+        _check_invert(x, nm)
+        if x.shape != u.shape:
+            raise RuntimeError(f"invert_displacement_adjoint: {nm} must have the shape of u")
+    _same(u, grad_out, v)
+    grad_out, u, v = grad_out.contiguous(), u.contiguous(), v.contiguous()
+    lam = torch.empty_like(u)
+    _call("lago_invert_disp_adjoint", u, _ptr(lam), _ptr(grad_out), _ptr(u), _ptr(v), dim, u.size(0), nx, ny, nz)
+    return lam
 
 
 def fluid_operator(Fmv, inverse, cosluts, sinluts, alpha, beta, gamma):
