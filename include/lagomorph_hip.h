@@ -39,6 +39,11 @@ extern "C" {
 
 #define LAGO_ABI_VERSION 5
 
+/* lago_gauss_smooth: the largest radius (taps on each side of the centre) a pass takes, and the border modes */
+#define LAGO_GAUSS_MAX_RADIUS 32
+#define LAGO_GAUSS_WRAP 0
+#define LAGO_GAUSS_ZERO 1
+
 /* ---- housekeeping --------------------------------------------------------- */
 
 /* replaces set_debug_mode (extension.cpp:105-107): when non-zero every entry
@@ -272,7 +277,26 @@ long long lago_reversed_launches(void);
      * det is not guarded: where the deformation folds (det M <= 0 or tiny) the IEEE result stands.  One gather     \
      * pass, no atomics, nothing cleared: identical from call to call.  lam must not overlap an input. */           \
     int lago_invert_disp_adjoint##SUF(REAL *lam, const REAL *grad_out, const REAL *u, const REAL *v, int dim,       \
-                                      int64_t nn, int64_t nx, int64_t ny, int64_t nz, void *stream);
+                                      int64_t nn, int64_t nx, int64_t ny, int64_t nz, void *stream);                \
+    /* gaussian_smooth: out = alpha * G_z G_y G_x in (+ out when accumulate), separable Gaussian filtering of       \
+     * `rows` = N*C scalar fields of extent (nx, ny[, nz]).  G_a is the 1-D correlation with the 2 r + 1 symmetric  \
+     * taps of axis a, r = radii[a] in 0..LAGO_GAUSS_MAX_RADIUS (0: the axis is left alone); taps holds             \
+     * LAGO_GAUSS_MAX_RADIUS + 1 doubles per axis, axis a's w_0 .. w_r at taps[a * (LAGO_GAUSS_MAX_RADIUS + 1)],    \
+     * rounded once to REAL.  radii and taps are HOST arrays of `dim` entries / blocks, read during the call and    \
+     * passed to the kernels by value (nothing of them is read later: the call may be captured in a graph).        \
+     * mode LAGO_GAUSS_WRAP: indices modulo the extent, however large r is relative to it; LAGO_GAUSS_ZERO:         \
+     * samples outside the grid are 0.  Both are self-adjoint.  One launch per axis with r > 0 (one copy launch     \
+     * when every r is 0), outermost axis first (of three, one that may run in place is taken second, with and      \
+     * without accumulate); the last one applies alpha and the accumulation.  scratch: one                         \
+     * tensor like in, needed when two or more axes have r > 0 (else may be NULL), clobbered.  in is not modified;  \
+     * out and scratch may not overlap in or each other.  No atomics: the same bits from call to call.  With       \
+     * accumulate and three passes the middle pass runs in place on scratch, which needs one axis that a workgroup  \
+     * stages whole (nz <= 1024, or nx or ny <= 64 (float) / 32 (double)): LAGO_ERR_INVALID otherwise.  An inf or    \
+     * NaN of `in` reaches outputs up to (r rounded up to 4) + 3 positions away along a filtered axis (zero padding  \
+     * taps are multiplied too); the all-zero-radii copy is exact.  No counterpart in the reference. */                                                                             \
+    int lago_gauss_smooth##SUF(REAL *out, const REAL *in, REAL *scratch, const int *radii, const double *taps,      \
+                               int mode, double alpha, int accumulate, int dim, int64_t rows, int64_t nx,           \
+                               int64_t ny, int64_t nz, void *stream);
 
 LAGO_DECLARE(float, _f32)
 LAGO_DECLARE(double, _f64)

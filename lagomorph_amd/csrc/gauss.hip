@@ -1,0 +1,410 @@
+// gaussian_smooth: separable Gaussian filtering of (rows, nx, ny, nz) fields -- gfx950 HIP kernels.
+//
+// out = alpha * G_z G_y G_x in (+ out), each G_a a 1-D correlation with 2 r_a + 1 symmetric taps along one axis, the border
+// either periodic ("wrap": indices modulo the extent, however large r_a is relative to it) or zero.  No counterpart in
+// the reference.  One launch per axis with r_a > 0, ping-pong between `out` and ONE scratch tensor, taps by value in the
+// kernel arguments, no atomics: every element is written once per pass by its own lane, from a sum in a fixed order.
+//
+// Both kernels stage a tile plus its halo in LDS with the border rule applied WHILE LOADING (a wrapped index or a zero),
+// so the filter itself is a plain sliding sum over LDS.  A lane owns four consecutive outputs along the filtered axis and
+// walks its window of 2 H + 4 staged values (H = r rounded up to 4; taps beyond r are zero) four at a time: each staged
+// value is read from LDS once per lane and feeds four fused multiply-adds, (2 H + 4) / 4 LDS reads per output instead of
+// 2 r + 1.
+//
+//   gauss_z_kernel   the contiguous axis.  A workgroup stages RT whole row segments (RT x (ZS + 2 H)) with coalesced loads;
+//                    a lane reads its window as aligned 4-vectors (lanes 16 / 32 bytes apart: conflict-free) and stores
+//                    one 4-vector.
+//   gauss_s_kernel   a strided axis (y: stride nz, x: stride ny nz).  Lanes run along the contiguous direction, so every
+//                    global access is a coalesced 256-byte row; the workgroup stages a (T + 2 H) x 64 slab and a lane walks
+//                    it down its own column (consecutive lanes, consecutive banks).
+//
+// A pass whose workgroups each stage the WHOLE extent of their lines (one z segment per row, one axis tile per column)
+// reads everything it needs before its barrier and writes after it, and no other workgroup touches those lines: such a
+// pass may run in place.  The three-pass accumulate form uses that (see gauss_impl).
+#include "common.hpp"
+
+namespace lago {
+
+constexpr int kGaussMaxRadius = LAGO_GAUSS_MAX_RADIUS;
+constexpr int kGaussTapSlots = kGaussMaxRadius + 4;   // w[0..r], zeros up to H + 3 <= 35
+constexpr int kGaussLanes = 64;                       // gauss_s_kernel: lanes along the contiguous direction
+constexpr int kGaussInFlight = 6;                     // staging: global loads a lane issues before it waits for the first
+
+// Non-finite input: a staged value is multiplied with every tap of its lane's window, the zero taps beyond r included
+// (the window is 2 H + 4 wide), so an inf or NaN reaches outputs up to H + 3 positions away along the filtered axis
+// instead of r (0 * inf = NaN).  Finite fields are unaffected; a pass of radius 0 copies its values untouched.
+//
+// Sums are taken in double for both precisions.  A float32 product of a tap and a value is then exact and a pass returns
+// the correctly rounded sum (up to 1e-16), so the error of a float32 result is the rounding of the stored intermediates,
+// relative to THEIR size -- which matters where the filter cancels its input (a wide kernel on a short periodic axis
+// returns the mean of the line, far smaller than the values).  (Assumed, not measured here: v_fma_f64 issues at the rate
+// of the unpacked v_fma_f32 on gfx950.)
+struct GaussTaps {
+    double w[kGaussTapSlots];   // w[|k|] for |k| <= r (already rounded to the field's precision), 0 beyond
+};
+
+struct GaussPass {
+    uint32_t n;          // extent of the filtered axis
+    uint32_t inner;      // elements between neighbours along it (1 for the z pass)
+    uint64_t outer;      // lines-of-lines: the tensor is (outer, n, inner)
+    int r, H;            // radius, radius rounded up to a multiple of 4
+    int wrap;            // 1: periodic, 0: zero outside
+    uint32_t bias;       // a multiple of n, >= H: (index + bias) is never negative
+    FastDiv dn;
+    int final, accumulate;   // the last pass applies alpha and may add onto out
+    // z pass: RT rows x one segment of ZS (a multiple of 4) outputs per workgroup
+    uint32_t ZS, nseg, nzc, RT, pitch;
+    FastDiv dseg, dzc, dpitch;
+    int vec;             // 4-vector stores allowed (nz % 4 == 0, base 16-byte (32 for double) aligned)
+    // strided pass: T (a multiple of 4) positions of the axis x 64 lanes per workgroup
+    uint32_t T, nat, nit;
+    FastDiv dat, dit;
+};
+
+template <typename R>
+__device__ __forceinline__ uint32_t gauss_resolve(const GaussPass &p, int idx, bool &inside) {
+    if (p.wrap) {
+        const uint32_t u = (uint32_t)(idx + (int)p.bias);
+        inside = true;
+        return u - p.dn.div(u) * p.n;
+    }
+    inside = idx >= 0 && idx < (int)p.n;
+    return inside ? (uint32_t)idx : 0u;
+}
+
+// The sliding sum of one lane: four outputs from the 2 H + 4 staged values at win[0], win[STRIDE], ...  Output o sits at
+// window position H + o, so value j carries tap j - H - o.  Taps are wave-uniform (kernel arguments, uniform index).
+template <typename R, typename LOAD4>
+__device__ __forceinline__ void gauss_slide(const GaussTaps &taps, int H, LOAD4 load4, double (&acc)[4]) {
+    double t[7];   // taps of k0 - 3 .. k0 + 3 for the four values at window offsets k0 .. k0 + 3 (relative to output 0)
+#pragma unroll
+    for (int j = 0; j < 3; ++j) t[j + 4] = 0.0;   // k = -H-3 .. -H-1: beyond every radius
+#pragma unroll
+    for (int o = 0; o < 4; ++o) acc[o] = 0.0;
+    if (H == 0) {   // radius 0 (the copy pass): the values themselves, no product with a zero tap (0 * inf), -0 kept
+        R v[4];
+        load4(0, v);
+#pragma unroll
+        for (int o = 0; o < 4; ++o) acc[o] = (double)v[o];
+        return;
+    }
+    const int steps = (2 * H + 4) >> 2;
+    for (int s = 0; s < steps; ++s) {
+        const int k0 = 4 * s - H;
+#pragma unroll
+        for (int j = 0; j < 3; ++j) t[j] = t[j + 4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int k = k0 + j;
+            t[j + 3] = taps.w[k < 0 ? -k : k];
+        }
+        R v[4];
+        load4(4 * s, v);
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+            for (int o = 0; o < 4; ++o) acc[o] = lg_fma(t[i - o + 3], (double)v[i], acc[o]);
+    }
+}
+
+template <typename R>
+__device__ __forceinline__ R gauss_epilogue(const GaussPass &p, R alpha, double dsum, R prev) {
+    const R sum = (R)dsum;
+    if (!p.final) return sum;
+    const R val = alpha * sum;
+    return p.accumulate ? prev + val : val;   // (accumulate is set on the last pass only)
+}
+
+extern __shared__ __attribute__((aligned(32))) unsigned char gauss_smem[];
+
+template <typename R>
+__global__ __launch_bounds__(kBlock) void gauss_z_kernel(R *out, const R *in, GaussTaps taps, R alpha, GaussPass p) {
+    typedef R vec4 __attribute__((ext_vector_type(4)));
+    R *lds = reinterpret_cast<R *>(gauss_smem);
+    const uint32_t rb = p.dseg.div(blockIdx.x);
+    const uint32_t seg = blockIdx.x - rb * p.nseg;
+    const uint64_t row0 = (uint64_t)rb * p.RT;
+    const int zs0 = (int)(seg * p.ZS);
+    const int lo = p.H - p.r, hi = p.H + (int)p.ZS + p.r;   // staged positions outside [lo, hi) carry zero taps only
+    const uint32_t staged = p.RT * p.pitch;
+    for (uint32_t e0 = threadIdx.x; e0 < staged; e0 += kGaussInFlight * kBlock) {   // loads first, then the LDS stores
+        R val[kGaussInFlight];
+#pragma unroll
+        for (int f = 0; f < kGaussInFlight; ++f) {
+            const uint32_t e = e0 + (uint32_t)f * kBlock;
+            const uint32_t rl = p.dpitch.div(e);
+            const int q = (int)(e - rl * p.pitch);
+            const uint64_t row = row0 + rl;
+            val[f] = (R)0;
+            if (e < staged && row < p.outer && q >= lo && q < hi) {
+                bool inside;
+                const uint32_t u = gauss_resolve<R>(p, zs0 - p.H + q, inside);
+                if (inside) val[f] = in[row * p.n + u];
+            }
+        }
+#pragma unroll
+        for (int f = 0; f < kGaussInFlight; ++f) {
+            const uint32_t e = e0 + (uint32_t)f * kBlock;
+            if (e < staged) lds[e] = val[f];
+        }
+    }
+    __syncthreads();
+    const uint32_t item = threadIdx.x;
+    if (item >= p.RT * p.nzc) return;
+    const uint32_t rl = p.dzc.div(item);
+    const uint32_t c = item - rl * p.nzc;
+    const uint64_t row = row0 + rl;
+    const uint32_t z0 = (uint32_t)zs0 + 4u * c;
+    if (row >= p.outer || z0 >= p.n) return;
+    const R *win = lds + rl * p.pitch + 4u * c;
+    double acc[4];
+    gauss_slide<R>(taps, p.H, [&](int off, R (&v)[4]) {
+        const vec4 x = *reinterpret_cast<const vec4 *>(win + off);
+        v[0] = x.x; v[1] = x.y; v[2] = x.z; v[3] = x.w;
+    }, acc);
+    R *o = out + row * p.n + z0;
+    if (p.vec && z0 + 3u < p.n) {
+        vec4 x = {(R)0, (R)0, (R)0, (R)0};
+        if (p.accumulate) x = *reinterpret_cast<const vec4 *>(o);
+        x.x = gauss_epilogue<R>(p, alpha, acc[0], x.x);
+        x.y = gauss_epilogue<R>(p, alpha, acc[1], x.y);
+        x.z = gauss_epilogue<R>(p, alpha, acc[2], x.z);
+        x.w = gauss_epilogue<R>(p, alpha, acc[3], x.w);
+        *reinterpret_cast<vec4 *>(o) = x;
+        return;
+    }
+    R prev[4] = {(R)0, (R)0, (R)0, (R)0};
+    if (p.accumulate) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+            if (z0 + (uint32_t)k < p.n) prev[k] = o[k];
+    }
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+        if (z0 + (uint32_t)k < p.n) o[k] = gauss_epilogue<R>(p, alpha, acc[k], prev[k]);
+}
+
+template <typename R>
+__global__ __launch_bounds__(kBlock) void gauss_s_kernel(R *out, const R *in, GaussTaps taps, R alpha, GaussPass p) {
+    R *lds = reinterpret_cast<R *>(gauss_smem);
+    uint32_t b = blockIdx.x;
+    uint32_t q1 = p.dit.div(b);
+    const uint32_t it = b - q1 * p.nit;
+    const uint32_t ot = p.dat.div(q1);
+    const uint32_t at = q1 - ot * p.nat;
+    const int a0 = (int)(at * p.T);
+    const uint32_t lane = threadIdx.x & (kGaussLanes - 1), grp = threadIdx.x / kGaussLanes;
+    const uint32_t ii = it * kGaussLanes + lane;
+    const bool lane_ok = ii < p.inner;
+    const size_t base = (size_t)ot * p.n * p.inner;   // (outer, n, inner): one line set
+    const R *src = in + base;
+    const uint32_t nrows = p.T + 2u * (uint32_t)p.H;
+    const int lo = p.H - p.r, hi = p.H + (int)p.T + p.r;
+    constexpr uint32_t kGroups = kBlock / kGaussLanes;
+    for (uint32_t q0 = grp; q0 < nrows; q0 += kGaussInFlight * kGroups) {   // loads first, then the LDS stores
+        R val[kGaussInFlight];
+#pragma unroll
+        for (int f = 0; f < kGaussInFlight; ++f) {
+            const uint32_t q = q0 + (uint32_t)f * kGroups;
+            val[f] = (R)0;
+            if (q < nrows && lane_ok && (int)q >= lo && (int)q < hi) {
+                bool inside;
+                const uint32_t u = gauss_resolve<R>(p, a0 - p.H + (int)q, inside);
+                if (inside) val[f] = src[(size_t)u * p.inner + ii];
+            }
+        }
+#pragma unroll
+        for (int f = 0; f < kGaussInFlight; ++f) {
+            const uint32_t q = q0 + (uint32_t)f * kGroups;
+            if (q < nrows) lds[q * kGaussLanes + lane] = val[f];
+        }
+    }
+    __syncthreads();
+    if (!lane_ok) return;
+    R *dst = out + base;
+    for (uint32_t c = grp; c < p.T / 4u; c += kGroups) {
+        const uint32_t a = (uint32_t)a0 + 4u * c;
+        if (a >= p.n) break;
+        const R *win = lds + (size_t)(4u * c) * kGaussLanes + lane;
+        double acc[4];
+        gauss_slide<R>(taps, p.H, [&](int off, R (&v)[4]) {
+#pragma unroll
+            for (int i = 0; i < 4; ++i) v[i] = win[(off + i) * kGaussLanes];
+        }, acc);
+        R *o = dst + (size_t)a * p.inner + ii;
+        R prev[4] = {(R)0, (R)0, (R)0, (R)0};
+        if (p.accumulate) {
+#pragma unroll
+            for (int k = 0; k < 4; ++k)
+                if (a + (uint32_t)k < p.n) prev[k] = o[(size_t)k * p.inner];
+        }
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+            if (a + (uint32_t)k < p.n) o[(size_t)k * p.inner] = gauss_epilogue<R>(p, alpha, acc[k], prev[k]);
+    }
+}
+
+static bool gauss_overlaps(const void *a, const void *b, size_t bytes) {
+    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
+    return x < y + bytes && y < x + bytes;
+}
+
+template <typename R>
+static bool gauss_plan(GaussPass &p, int axis, int r, int mode, int64_t rows, const Geom &g, const R *out) {
+    const int64_t ext[3] = {g.nx, g.ny, g.nz};
+    p = GaussPass();
+    p.n = (uint32_t)ext[axis];
+    p.inner = axis == 2 ? 1u : axis == 1 ? (uint32_t)g.nz : (uint32_t)(g.ny * g.nz);
+    p.outer = (uint64_t)rows * (axis == 2 ? (uint64_t)g.nx * g.ny : axis == 1 ? (uint64_t)g.nx : 1ull);
+    p.r = r;
+    p.H = (r + 3) & ~3;
+    p.wrap = mode == LAGO_GAUSS_WRAP;
+    p.bias = p.n * (uint32_t)((p.H + (int)p.n - 1) / (int)p.n);
+    p.dn = FastDiv(p.n);
+    if (axis == 2) {
+        const uint32_t n4 = (p.n + 3u) & ~3u;
+        p.ZS = n4 < 1024u ? n4 : 1024u;
+        p.nseg = (p.n + p.ZS - 1) / p.ZS;
+        p.nzc = p.ZS / 4;
+        p.RT = kBlock / p.nzc;
+        if (p.RT > 32) p.RT = 32;
+        if (p.RT < 1) p.RT = 1;
+        p.pitch = p.ZS + 2u * (uint32_t)p.H;
+        p.dseg = FastDiv(p.nseg);
+        p.dzc = FastDiv(p.nzc);
+        p.dpitch = FastDiv(p.pitch);
+        p.vec = p.n % 4 == 0 && (uintptr_t)out % (4 * sizeof(R)) == 0;
+        const uint64_t nb = (p.outer + p.RT - 1) / p.RT * p.nseg;
+        return nb < (1ull << 31);
+    }
+    const uint32_t tmax = sizeof(R) == 4 ? 64u : 32u;   // (T + 2 H) x 64 elements: at most 32 KiB (float) / 48 KiB (double) of LDS
+    p.nat = (p.n + tmax - 1) / tmax;
+    p.T = ((p.n + p.nat - 1) / p.nat + 3u) & ~3u;
+    p.nat = (p.n + p.T - 1) / p.T;
+    p.nit = (p.inner + kGaussLanes - 1) / kGaussLanes;
+    p.dat = FastDiv(p.nat);
+    p.dit = FastDiv(p.nit);
+    const uint64_t nb = p.outer * p.nat * p.nit;
+    return nb < (1ull << 31);
+}
+
+template <typename R>
+static uint32_t gauss_blocks(const GaussPass &p, int axis) {
+    if (axis == 2) return (uint32_t)((p.outer + p.RT - 1) / p.RT * p.nseg);
+    return (uint32_t)(p.outer * p.nat * p.nit);
+}
+
+// whether every workgroup of the pass stages the whole extent of its lines: the pass may then run in place
+static bool gauss_whole_lines(const GaussPass &p, int axis) { return axis == 2 ? p.nseg == 1 : p.nat == 1; }
+
+template <typename R>
+static void gauss_launch(const GaussPass &p, int axis, R *dst, const R *src, const GaussTaps &taps, R alpha,
+                         hipStream_t s) {
+    const uint32_t nb = gauss_blocks<R>(p, axis);
+    if (axis == 2) {
+        const size_t smem = (size_t)p.RT * p.pitch * sizeof(R);
+        hipLaunchKernelGGL((gauss_z_kernel<R>), dim3(nb), dim3(kBlock), smem, s, dst, src, taps, alpha, p);
+    } else {
+        const size_t smem = (size_t)(p.T + 2u * (uint32_t)p.H) * kGaussLanes * sizeof(R);
+        hipLaunchKernelGGL((gauss_s_kernel<R>), dim3(nb), dim3(kBlock), smem, s, dst, src, taps, alpha, p);
+    }
+}
+
+template <typename R>
+static int gauss_impl(R *out, const R *in, R *scratch, const int *radii, const double *taps, int mode, double alpha,
+                      int accumulate, int dim, int64_t rows, int64_t nx, int64_t ny, int64_t nz, void *stream) {
+    if (dim != 2 && dim != 3) return fail_invalid("Only two- and three-dimensional gaussian smoothing is supported");
+    if (mode != LAGO_GAUSS_WRAP && mode != LAGO_GAUSS_ZERO)
+        return fail_invalid("gaussian_smooth: unknown border mode %d", mode);
+    if (!radii) return fail_invalid("gaussian_smooth: null radii");
+    int rad[3] = {0, 0, 0};   // per axis of the (nx, ny, nz) geometry; a 2D field is (1, H, W)
+    const double *tp[3] = {nullptr, nullptr, nullptr};
+    for (int a = 0; a < dim; ++a) {
+        const int r = radii[a];
+        if (r < 0 || r > kGaussMaxRadius)
+            return fail_invalid("gaussian_smooth: radius %d is outside 0..%d (wider kernels: use the FFT operator)", r,
+                                kGaussMaxRadius);
+        if (r > 0 && !taps) return fail_invalid("gaussian_smooth: null taps");
+        rad[a + 3 - dim] = r;
+        tp[a + 3 - dim] = taps ? taps + (size_t)a * (kGaussMaxRadius + 1) : nullptr;
+    }
+    Geom g;
+    if (!make_geom(g, dim, rows, nx, ny, nz)) return fail_invalid("gaussian_smooth: bad extent");
+    if (g.nblocks == 0) return LAGO_OK;
+    if (!out || !in) return fail_invalid("gaussian_smooth: null pointer");
+    const size_t bytes = (size_t)rows * g.nvox * sizeof(R);
+    if (gauss_overlaps(out, in, bytes)) return fail_invalid("gaussian_smooth: out must not alias in");
+
+    // the passes, outermost axis first.  Three passes that accumulate onto `out` cannot use it as a stage: the middle
+    // one runs in place on the scratch tensor, which needs a pass that stages whole lines (see the head of this file);
+    // such a pass is moved to the middle whether or not this call accumulates
+    int order[3], m = 0;
+    for (int a = 0; a < 3; ++a)
+        if (rad[a] > 0) order[m++] = a;
+    GaussPass pass[3];
+    GaussTaps tw[3];
+    if (m == 0) {   // nothing to filter: the z pass with the single tap 1 is the copy / alpha / accumulate pass
+        order[m++] = 2;
+    }
+    for (int i = 0; i < m; ++i) {
+        const int a = order[i];
+        if (!gauss_plan<R>(pass[i], a, rad[a], mode, rows, g, out)) return fail_invalid("gaussian_smooth: bad extent");
+        for (int k = 0; k < kGaussTapSlots; ++k) tw[i].w[k] = 0.0;
+        if (rad[a] == 0) tw[i].w[0] = 1.0;
+        for (int k = 0; k <= rad[a]; ++k)
+            if (rad[a] > 0) tw[i].w[k] = (double)(R)tp[a][k];   // rounded once to the field's precision
+    }
+    if (m == 3) {   // (the same order with and without accumulate: the same sums, the same bits)
+        int mid = -1;
+        for (int i = 0; i < 3 && mid < 0; ++i)
+            if (gauss_whole_lines(pass[i], order[i])) mid = i;
+        if (mid < 0 && accumulate)
+            return fail_invalid("gaussian_smooth: accumulate with three passes needs one axis staged whole "
+                                "(nz <= 1024, or nx or ny <= %d)", sizeof(R) == 4 ? 64 : 32);
+        if (mid >= 0 && mid != 1) {
+            std::swap(pass[mid], pass[1]);
+            std::swap(tw[mid], tw[1]);
+            std::swap(order[mid], order[1]);
+        }
+    }
+    if (m >= 2) {
+        if (!scratch) return fail_invalid("gaussian_smooth: two or more passes need the scratch tensor");
+        if (gauss_overlaps(scratch, in, bytes) || gauss_overlaps(scratch, out, bytes))
+            return fail_invalid("gaussian_smooth: scratch must not alias in or out");
+    }
+    // pass.vec was planned against `out`; the scratch tensor must allow the same stores
+    const bool scratch_vec = scratch && (uintptr_t)scratch % (4 * sizeof(R)) == 0;
+    hipStream_t s = (hipStream_t)stream;
+    const R al = (R)alpha;
+    const R *src = in;
+    for (int i = 0; i < m; ++i) {
+        const bool last = i == m - 1;
+        R *dst;
+        if (last) dst = out;
+        else if (m == 2) dst = scratch;
+        else if (accumulate) dst = scratch;                 // in -> scratch -> scratch (in place) -> out
+        else dst = i == 0 ? out : scratch;                  // in -> out -> scratch -> out
+        GaussPass p = pass[i];
+        p.final = last;
+        p.accumulate = last && accumulate;
+        if (dst == scratch) p.vec = p.vec && scratch_vec;
+        gauss_launch<R>(p, order[i], dst, src, tw[i], al, s);
+        src = dst;
+    }
+    return finish_launch(s, "gaussian_smooth");
+}
+
+}  // namespace lago
+
+extern "C" {
+#define LAGO_DEFINE(REAL, SUF)                                                                                      \
+    int lago_gauss_smooth##SUF(REAL *out, const REAL *in, REAL *scratch, const int *radii, const double *taps,     \
+                               int mode, double alpha, int accumulate, int dim, int64_t rows, int64_t nx,          \
+                               int64_t ny, int64_t nz, void *stream) {                                             \
+        return lago::gauss_impl<REAL>(out, in, scratch, radii, taps, mode, alpha, accumulate, dim, rows, nx, ny,   \
+                                      nz, stream);                                                                  \
+    }
+LAGO_DEFINE(float, _f32)
+LAGO_DEFINE(double, _f64)
+#undef LAGO_DEFINE
+}

@@ -73,6 +73,7 @@ _SIGS = {
     "lago_jacdet_backward": [_vp, _vp, _vp, _int, _int, _i64, _i64, _i64, _i64, _vp],
     "lago_invert_disp_forward": [_vp, _vp, _int, _int, _i64, _i64, _i64, _i64, _vp],
     "lago_invert_disp_adjoint": [_vp, _vp, _vp, _vp, _int, _i64, _i64, _i64, _i64, _vp],
+    "lago_gauss_smooth": [_vp, _vp, _vp, _vp, _vp, _int, _dbl, _int, _int, _i64, _i64, _i64, _i64, _vp],
     "lago_fluid_metric": [_vp, _vp, _vp, _i64, _int, _vp, _vp, _vp, _vp, _vp, _vp, _dbl, _dbl, _dbl, _int, _i64, _i64,
                           _i64, _i64, _vp],
     "lago_fluid_metric_scaled": [_vp, _vp, _vp, _i64, _int, _vp, _vp, _vp, _vp, _vp, _vp, _dbl, _dbl, _dbl, _int, _i64,
@@ -521,6 +522,68 @@ def invert_displacement_adjoint(grad_out, u, v):
     lam = torch.empty_like(u)
     _call("lago_invert_disp_adjoint", u, _ptr(lam), _ptr(grad_out), _ptr(u), _ptr(v), dim, u.size(0), nx, ny, nz)
     return lam
+
+
+GAUSS_MAX_RADIUS = 32   # LAGO_GAUSS_MAX_RADIUS of include/lagomorph_hip.h
+GAUSS_MODES = {"wrap": 0, "zero": 1}   # LAGO_GAUSS_WRAP / LAGO_GAUSS_ZERO
+
+
+def gaussian_smooth_forward(x, radii, taps, mode, alpha=1.0, out=None, accumulate=False):
+    """alpha * G x (+ out when accumulate): separable filtering of x (N, C, *sp) with symmetric taps, one kernel per
+    axis with a radius > 0 (csrc/gauss.hip).  radii: one int per spatial axis; taps: per axis the 2 r + 1 float64 taps
+    (ignored where r == 0); mode "wrap" or "zero".  The result is `out` when given (like x, not overlapping it), a new
+    tensor otherwise.  One scratch tensor like x is allocated here when two or more axes are filtered.  Not in the
+    reference; no CPU path."""
+    if not isinstance(x, torch.Tensor):
+        raise TypeError("x must be a torch.Tensor")
+    _suffix(x)
+    dim, nx, ny, nz = _spatial(x)
+    if dim not in (2, 3):
+        raise RuntimeError("Only two- and three-dimensional gaussian smoothing is supported")
+    if mode not in GAUSS_MODES:
+        raise ValueError(f"gaussian_smooth: unknown mode {mode!r} (one of {sorted(GAUSS_MODES)})")
+    radii = [int(r) for r in radii]
+    if len(radii) != dim or len(taps) != dim:
+        raise ValueError(f"gaussian_smooth: {dim} radii and tap vectors are needed, one per spatial axis")
+    half = (ctypes.c_double * (dim * (GAUSS_MAX_RADIUS + 1)))()
+    for a, r in enumerate(radii):
+        if r < 0 or r > GAUSS_MAX_RADIUS:
+            raise ValueError(f"gaussian_smooth: radius {r} on axis {a} is outside 0..{GAUSS_MAX_RADIUS}")
+        if r > 0:
+            t = [float(v) for v in taps[a]]
+            if len(t) != 2 * r + 1:
+                raise ValueError(f"gaussian_smooth: axis {a} needs {2 * r + 1} taps, got {len(t)}")
+            if any(t[r + k] != t[r - k] for k in range(1, r + 1)):
+                raise ValueError("gaussian_smooth: the taps must be symmetric")
+            for k in range(r + 1):
+                half[a * (GAUSS_MAX_RADIUS + 1) + k] = t[r + k]
+    if accumulate and out is None:
+        raise RuntimeError("gaussian_smooth: accumulate needs out")
+    if not x.is_cuda:
+        raise RuntimeError("x must be a CUDA tensor")
+    x = x.contiguous()
+    if out is None:
+        out = torch.empty_like(x)
+    else:
+        _check_input(out, "out")
+        _same(x, out)
+        if out.shape != x.shape:
+            raise RuntimeError("gaussian_smooth: out must have the shape of x")
+        if _overlaps(out, x):
+            raise RuntimeError("gaussian_smooth: out must not overlap x")
+    scratch = torch.empty_like(x) if sum(r > 0 for r in radii) >= 2 else None
+    rad = (ctypes.c_int * dim)(*radii)
+    whole = 64 if x.dtype == torch.float32 else 32
+    if accumulate and sum(r > 0 for r in radii) == 3 and nz > 1024 and nx > whole and ny > whole:
+        # the one shape class whose three-pass accumulate form has no in-place middle pass (include/lagomorph_hip.h):
+        # the sum is taken here instead, from alpha * G x in a tensor of its own
+        term = torch.empty_like(x)
+        _call("lago_gauss_smooth", x, _ptr(term), _ptr(x), _ptr(scratch), rad, half, GAUSS_MODES[mode], float(alpha), 0,
+              dim, x.size(0) * x.size(1), nx, ny, nz)
+        return out.add_(term)
+    _call("lago_gauss_smooth", x, _ptr(out), _ptr(x), _ptr(scratch), rad, half, GAUSS_MODES[mode], float(alpha),
+          int(bool(accumulate)), dim, x.size(0) * x.size(1), nx, ny, nz)
+    return out
 
 
 def fluid_operator(Fmv, inverse, cosluts, sinluts, alpha, beta, gamma):

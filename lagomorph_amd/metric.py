@@ -10,7 +10,7 @@ import itertools
 import numpy as np
 import torch
 
-from . import lagomorph_ext
+from . import lagomorph_ext, smooth
 
 
 def _rfft(x, spatial_dim):
@@ -121,6 +121,60 @@ class FluidMetric(object):
     def flat(self, m, out=None):
         """velocity -> momentum (apply the differential operator)."""
         return self.operator(m, inverse=False)
+
+
+class GaussianSumOperator(torch.autograd.Function):
+    """out_scale * sum_i weights[i] * G_{sigmas[i]} m, every term after the first accumulated inside its last kernel
+    (lago_gauss_smooth's epilogue): no elementwise pass for the sum.  Self-adjoint, like each term."""
+
+    @staticmethod
+    def forward(ctx, metric, m, out_scale):
+        ctx.metric, ctx.out_scale = metric, out_scale
+        m = m.contiguous()
+        out = None
+        for sigma, w in zip(metric.sigmas, metric.weights):
+            radii, taps = smooth._plan(m, sigma, metric.truncate, metric.mode)
+            out = lagomorph_ext.gaussian_smooth_forward(m, radii, taps, metric.mode, alpha=out_scale * w, out=out,
+                                                        accumulate=out is not None)
+        return out
+
+    @staticmethod
+    def backward(ctx, outgrad):
+        return None, ctx.metric.sharp(outgrad, out_scale=ctx.out_scale), None
+
+
+class GaussianMetric(object):
+    """The Gaussian (RKHS) kernel metric of LDDMM, or a sum of Gaussians at several widths:
+
+        sharp(m) = sum_i weights[i] * gaussian_smooth(m, sigmas[i], truncate, mode)
+
+    sigmas: one entry per Gaussian, each a number or one number per spatial axis (voxels); weights default to ones.
+    Not in the reference.  It serves as the `metric` of expmap, expmap_advect, EPDiff_step and lddmm_step through
+    their general branches (the fused fast paths are FluidMetric's).
+
+    `flat` is not available: the inverse of a Gaussian is not a bounded operator (its symbol decays like
+    exp(-sigma^2 |k|^2 / 2), so the inverse amplifies the highest frequencies without limit), hence
+    lddmm_step(..., momentum_preconditioning=True) cannot be used with this metric."""
+
+    def __init__(self, sigmas, weights=None, mode="wrap", truncate=4.0):
+        self.sigmas = list(sigmas)
+        if not self.sigmas:
+            raise ValueError("GaussianMetric: at least one sigma is needed")
+        self.weights = [1.0] * len(self.sigmas) if weights is None else [float(w) for w in weights]
+        if len(self.weights) != len(self.sigmas):
+            raise ValueError("GaussianMetric: one weight per sigma is needed")
+        if mode not in lagomorph_ext.GAUSS_MODES:
+            raise ValueError(f"GaussianMetric: unknown mode {mode!r}")
+        self.mode = mode
+        self.truncate = float(truncate)
+
+    def sharp(self, m, out_scale=1.0):
+        """momentum -> velocity: out_scale * sum_i weights[i] * G_i m."""
+        return GaussianSumOperator.apply(self, m, float(out_scale))
+
+    def flat(self, m, out=None):
+        raise NotImplementedError("GaussianMetric.flat: the inverse of a Gaussian kernel is not a bounded operator "
+                                  "(momentum_preconditioning is not available with this metric)")
 
 
 class Metric:
