@@ -344,10 +344,9 @@ static int affine_splat_boxes(R *d_I, const R *go, const R *A, const R *T, int n
     // the items the box kernel leaves: the general tiled kernel (or, where it does not apply, nothing: handled below)
     const int rc = affine_splat_lds<R>(d_I, go, A, T, nc, nn, g, bc, s, 1);
     if (rc != 0) return rc;   // shape not supported by the general kernel either: the caller's plain kernel does all items
-    if (bc)
-        hipLaunchKernelGGL((affine_splat_box_kernel<R, true>), dim3(bg.total), dim3(kBlock), smem, s, d_I, go, A, T, nc, bg);
-    else
-        hipLaunchKernelGGL((affine_splat_box_kernel<R, false>), dim3(bg.total), dim3(kBlock), smem, s, d_I, go, A, T, nc, bg);
+    with_flags([&](auto BC) {
+        hipLaunchKernelGGL((affine_splat_box_kernel<R, BC()>), dim3(bg.total), dim3(kBlock), smem, s, d_I, go, A, T, nc, bg);
+    }, bc);
     note_path(LP_SPLAT_AFFINE_BOX);
     return 0;
 }
@@ -632,42 +631,14 @@ static int affine_forward_impl(R *out, const R *I, const R *A, const R *T, int d
     // 134 MB in all: no difference).  The kernel is bound by the rate of its four pair gathers per output value, like
     // every gather kernel of the library (profiles/r05_affine_regrid_forward.md): several voxels per lane changed nothing.
     const bool big = (double)(nn + (bc ? 1 : nn)) * nc * g.nvox * sizeof(R) > 256.0 * 1024 * 1024;
-#define LAUNCH(D, B)                                                                                                     \
-    do {                                                                                                                 \
-        if (big) hipLaunchKernelGGL((affine_fwd_kernel<R, D, B, 1>), dim3(g.nblocks), dim3(kBlock), 0, s, out, I, A, T, (int)nc, g); \
-        else hipLaunchKernelGGL((affine_fwd_kernel<R, D, B, 0>), dim3(g.nblocks), dim3(kBlock), 0, s, out, I, A, T, (int)nc, g);     \
-    } while (0)
-    if (dim == 3) {
-        if (bc) LAUNCH(3, true); else LAUNCH(3, false);
-    } else {
-        if (bc) LAUNCH(2, true); else LAUNCH(2, false);
-    }
-#undef LAUNCH
+    with_dim(dim, [&](auto DIM) {
+        with_flags([&](auto BC, auto BIG) {
+            constexpr int NTS = BIG() ? 1 : 0;
+            hipLaunchKernelGGL((affine_fwd_kernel<R, DIM(), BC(), NTS>), dim3(g.nblocks), dim3(kBlock), 0, s, out, I, A, T,
+                               (int)nc, g);
+        }, bc != 0, big);
+    });
     return finish_launch(s, "affine_interp_forward");
-}
-
-template <typename R, int DIM, bool BC>
-static void launch_affine_bwd(R *d_I, R *d_A, R *d_T, const R *go, const R *I, const R *A, const R *T, int nc,
-                              const Geom &g, int64_t nn, bool nI, bool nA, bool nT, hipStream_t s) {
-    // ~4096 workgroups in total, at most one per 256-voxel chunk
-    uint32_t gx = (uint32_t)((4096 + nn - 1) / nn);
-    if (gx > g.nbx) gx = g.nbx;
-    if (gx < 1) gx = 1;
-#define LAUNCH(a, b, c)                                                                                             \
-    hipLaunchKernelGGL((affine_bwd_kernel<R, DIM, BC, a, b, c>), dim3(gx, (uint32_t)nn), dim3(kBlock), 0, s, d_I, d_A,  \
-                       d_T, go, I, A, T, nc, g)
-    const int m = (nI ? 4 : 0) | (nA ? 2 : 0) | (nT ? 1 : 0);
-    switch (m) {
-        case 7: LAUNCH(true, true, true); break;
-        case 6: LAUNCH(true, true, false); break;
-        case 5: LAUNCH(true, false, true); break;
-        case 4: LAUNCH(true, false, false); break;
-        case 3: LAUNCH(false, true, true); break;
-        case 2: LAUNCH(false, true, false); break;
-        case 1: LAUNCH(false, false, true); break;
-        default: break;
-    }
-#undef LAUNCH
 }
 
 template <typename R>
@@ -696,13 +667,17 @@ static int affine_backward_impl(R *d_I, R *d_A, R *d_T, const R *go, const R *I,
         if (rc == 0) need_I = 0;
     }
     if (g.nblocks && nc && (need_I || need_A || need_T)) {
-        if (dim == 3) {
-            if (bc) launch_affine_bwd<R, 3, true>(d_I, d_A, d_T, go, I, A, T, (int)nc, g, nn, need_I, need_A, need_T, s);
-            else launch_affine_bwd<R, 3, false>(d_I, d_A, d_T, go, I, A, T, (int)nc, g, nn, need_I, need_A, need_T, s);
-        } else {
-            if (bc) launch_affine_bwd<R, 2, true>(d_I, d_A, d_T, go, I, A, T, (int)nc, g, nn, need_I, need_A, need_T, s);
-            else launch_affine_bwd<R, 2, false>(d_I, d_A, d_T, go, I, A, T, (int)nc, g, nn, need_I, need_A, need_T, s);
-        }
+        // ~4096 workgroups in total, at most one per 256-voxel chunk
+        uint32_t gx = (uint32_t)((4096 + nn - 1) / nn);
+        if (gx > g.nbx) gx = g.nbx;
+        if (gx < 1) gx = 1;
+        with_dim(dim, [&](auto DIM) {
+            with_flags([&](auto BC, auto NEED_I, auto NEED_A, auto NEED_T) {
+                if constexpr (NEED_I() || NEED_A() || NEED_T())   // (none: not reached, and no such kernel exists)
+                    hipLaunchKernelGGL((affine_bwd_kernel<R, DIM(), BC(), NEED_I(), NEED_A(), NEED_T()>),
+                                       dim3(gx, (uint32_t)nn), dim3(kBlock), 0, s, d_I, d_A, d_T, go, I, A, T, (int)nc, g);
+            }, bc != 0, need_I != 0, need_A != 0, need_T != 0);
+        });
     }
     return finish_launch(s, "affine_interp_backward");
 }
@@ -741,13 +716,13 @@ static int regrid_forward_impl(R *out, const R *I, int dim, int64_t nn, int64_t 
     hipStream_t s = (hipStream_t)stream;
     // (non-temporal stores once input + output exceed the Infinity Cache: 80^3 -> 160^3 at 8 x 3 planes 260 -> 190 us)
     const bool big = ((double)nn * nc * ((double)g.nvox + (double)rp.nx * rp.ny * rp.nz)) * sizeof(R) > 256.0 * 1024 * 1024;
-#define LAUNCH(D)                                                                                                        \
-    do {                                                                                                                 \
-        if (big) hipLaunchKernelGGL((regrid_fwd_kernel<R, D, 1>), dim3(g.nblocks), dim3(kBlock), 0, s, out, I, (int)(nn * nc), g, rp); \
-        else hipLaunchKernelGGL((regrid_fwd_kernel<R, D, 0>), dim3(g.nblocks), dim3(kBlock), 0, s, out, I, (int)(nn * nc), g, rp);     \
-    } while (0)
-    if (dim == 3) LAUNCH(3); else LAUNCH(2);
-#undef LAUNCH
+    with_dim(dim, [&](auto DIM) {
+        with_flags([&](auto BIG) {
+            constexpr int NTS = BIG() ? 1 : 0;
+            hipLaunchKernelGGL((regrid_fwd_kernel<R, DIM(), NTS>), dim3(g.nblocks), dim3(kBlock), 0, s, out, I,
+                               (int)(nn * nc), g, rp);
+        }, big);
+    });
     return finish_launch(s, "regrid_forward");
 }
 
@@ -774,10 +749,9 @@ static int regrid_backward_impl(R *d_I, const R *go, int dim, int64_t nn, int64_
             }
         }
         note_path(LP_SPLAT_GLOBAL);
-        if (dim == 3)
-            hipLaunchKernelGGL((regrid_bwd_kernel<R, 3>), dim3(g.nblocks), dim3(kBlock), 0, s, d_I, go, (int)(nn * nc), g, rp);
-        else
-            hipLaunchKernelGGL((regrid_bwd_kernel<R, 2>), dim3(g.nblocks), dim3(kBlock), 0, s, d_I, go, (int)(nn * nc), g, rp);
+        with_dim(dim, [&](auto DIM) {
+            hipLaunchKernelGGL((regrid_bwd_kernel<R, DIM()>), dim3(g.nblocks), dim3(kBlock), 0, s, d_I, go, (int)(nn * nc), g, rp);
+        });
     }
     return finish_launch(s, "regrid_backward");
 }

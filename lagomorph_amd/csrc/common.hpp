@@ -138,6 +138,19 @@ inline bool make_geom(Geom &g, int dim, int64_t nn, int64_t nx, int64_t ny, int6
     return true;
 }
 
+// argument checks that several entry points share
+inline bool overlaps(const void *a, const void *b, size_t bytes) {  // two buffers of `bytes` bytes each
+    const uintptr_t p = (uintptr_t)a, q = (uintptr_t)b;
+    return p < q + bytes && q < p + bytes;
+}
+inline bool thin(int dim, int64_t nx, int64_t ny, int64_t nz) {  // an extent the central differences cannot take
+    return nx <= 1 || ny <= 1 || (dim == 3 && nz <= 1);
+}
+
+}  // namespace lago
+#include "launch.hpp"   // with_flags / with_dim / with_int, launch, slab_grid (needs Geom)
+namespace lago {
+
 // ---------------------------------------------------------------- device side
 
 // Workgroups are dealt round-robin over the 8 XCDs (block b -> XCD b % 8).  Map

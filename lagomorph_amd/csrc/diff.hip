@@ -400,10 +400,6 @@ __global__ __launch_bounds__(kBlock) void jacdet_bwd_kernel(R *__restrict__ d_u,
 
 // ------------------------------------------------------------------ host entry points
 
-static bool thin(int dim, int64_t nx, int64_t ny, int64_t nz) {
-    return nx <= 1 || ny <= 1 || (dim == 3 && nz <= 1);
-}
-
 template <typename R>
 static int jtv_forward_impl(R *out, const R *v, const R *w, int disp, int trans, int dim, int64_t nn, int64_t nc,
                             int64_t nx, int64_t ny, int64_t nz, void *stream) {
@@ -418,17 +414,12 @@ static int jtv_forward_impl(R *out, const R *v, const R *w, int disp, int trans,
     if (g.nblocks == 0 || nc == 0) return LAGO_OK;
     if (!out || !v || !w) return fail_invalid("jacobian_times_vectorfield_forward: null pointer");
     hipStream_t s = (hipStream_t)stream;
-#define LAUNCH(D, DS, TR) \
-    hipLaunchKernelGGL((jtv_fwd_kernel<R, D, DS, TR>), dim3(g.nblocks), dim3(kBlock), 0, s, out, v, w, (int)nc, g)
-#define BY_FLAGS(D)                                        \
-    do {                                                   \
-        if (disp && trans) LAUNCH(D, true, true);          \
-        else if (disp) LAUNCH(D, true, false);             \
-        else if (trans) LAUNCH(D, false, true);            \
-        else LAUNCH(D, false, false);                      \
-    } while (0)
-    if (dim == 3) BY_FLAGS(3); else BY_FLAGS(2);
-#undef LAUNCH
+    with_dim(dim, [&](auto DIM) {
+        with_flags([&](auto DISP, auto TRANS) {
+            hipLaunchKernelGGL((jtv_fwd_kernel<R, DIM(), DISP(), TRANS()>), dim3(g.nblocks), dim3(kBlock), 0, s, out, v,
+                               w, (int)nc, g);
+        }, disp != 0, trans != 0);
+    });
     return finish_launch(s, "jacobian_times_vectorfield_forward");
 }
 
@@ -451,12 +442,12 @@ static int jtv_backward_impl(R *d_v, R *d_w, const R *go, const R *v, const R *w
         LAGO_HIP_TRY(hipMemsetAsync(d_w, 0, (size_t)nn * dim * g.nvox * sizeof(R), s));
         return finish_launch(s, "jacobian_times_vectorfield_backward");
     }
-#define LAUNCH(D, DS, TR)                                                                                       \
-    hipLaunchKernelGGL((jtv_bwd_kernel<R, D, DS, TR>), dim3(g.nblocks), dim3(kBlock), 0, s, d_v, d_w, go, v, w, \
-                       (int)nc, g, acc_v)
-    if (dim == 3) BY_FLAGS(3); else BY_FLAGS(2);
-#undef LAUNCH
-#undef BY_FLAGS
+    with_dim(dim, [&](auto DIM) {
+        with_flags([&](auto DISP, auto TRANS) {
+            hipLaunchKernelGGL((jtv_bwd_kernel<R, DIM(), DISP(), TRANS()>), dim3(g.nblocks), dim3(kBlock), 0, s, d_v,
+                               d_w, go, v, w, (int)nc, g, acc_v);
+        }, disp != 0, trans != 0);
+    });
     return finish_launch(s, "jacobian_times_vectorfield_backward");
 }
 
@@ -472,10 +463,9 @@ static int jtv_adjoint_forward_impl(R *out, const R *z, const R *w, int dim, int
     if (g.nblocks == 0 || nc == 0) return LAGO_OK;
     if (!out || !z || !w) return fail_invalid("jacobian_times_vectorfield_adjoint_forward: null pointer");
     hipStream_t s = (hipStream_t)stream;
-    if (dim == 3)
-        hipLaunchKernelGGL((jtv_adj_fwd_kernel<R, 3>), dim3(g.nblocks), dim3(kBlock), 0, s, out, z, w, (int)nc, g);
-    else
-        hipLaunchKernelGGL((jtv_adj_fwd_kernel<R, 2>), dim3(g.nblocks), dim3(kBlock), 0, s, out, z, w, (int)nc, g);
+    with_dim(dim, [&](auto DIM) {
+        hipLaunchKernelGGL((jtv_adj_fwd_kernel<R, DIM()>), dim3(g.nblocks), dim3(kBlock), 0, s, out, z, w, (int)nc, g);
+    });
     return finish_launch(s, "jacobian_times_vectorfield_adjoint_forward");
 }
 
@@ -491,10 +481,9 @@ static int ad_star_small_impl(R *out, const R *v, const R *m, int dim, int64_t n
     if (!out || !v || !m) return fail_invalid("ad_star: null pointer");
     if (out == v || out == m) return fail_invalid("ad_star: out may not alias an input");
     hipStream_t s = (hipStream_t)stream;
-    if (dim == 3)
-        hipLaunchKernelGGL((ad_star_small_kernel<R, 3>), dim3(g.nblocks), dim3(kBlock), 0, s, out, v, m, g);
-    else
-        hipLaunchKernelGGL((ad_star_small_kernel<R, 2>), dim3(g.nblocks), dim3(kBlock), 0, s, out, v, m, g);
+    with_dim(dim, [&](auto DIM) {
+        hipLaunchKernelGGL((ad_star_small_kernel<R, DIM()>), dim3(g.nblocks), dim3(kBlock), 0, s, out, v, m, g);
+    });
     return finish_launch(s, "ad_star");
 }
 
@@ -511,10 +500,9 @@ static int jtv_adjoint_backward_impl(R *d_v, R *d_w, const R *go, const R *v, co
     if (!d_v || !d_w || !go || !v || !w)
         return fail_invalid("jacobian_times_vectorfield_adjoint_backward: null pointer");
     hipStream_t s = (hipStream_t)stream;
-    if (dim == 3)
-        hipLaunchKernelGGL((jtv_adj_bwd_kernel<R, 3>), dim3(g.nblocks), dim3(kBlock), 0, s, d_v, d_w, go, v, w, g);
-    else
-        hipLaunchKernelGGL((jtv_adj_bwd_kernel<R, 2>), dim3(g.nblocks), dim3(kBlock), 0, s, d_v, d_w, go, v, w, g);
+    with_dim(dim, [&](auto DIM) {
+        hipLaunchKernelGGL((jtv_adj_bwd_kernel<R, DIM()>), dim3(g.nblocks), dim3(kBlock), 0, s, d_v, d_w, go, v, w, g);
+    });
     return finish_launch(s, "jacobian_times_vectorfield_adjoint_backward");
 }
 
@@ -529,19 +517,14 @@ static int jacdet_impl(R *out, const R *aux, const R *u, bool backward, int disp
     if (g.nblocks == 0) return LAGO_OK;
     if (!out || !u || (backward && !aux)) return fail_invalid("%s: null pointer", what);
     hipStream_t s = (hipStream_t)stream;
-#define LAUNCH(D, DS)                                                                                               \
-    do {                                                                                                            \
-        if (backward)                                                                                               \
-            hipLaunchKernelGGL((jacdet_bwd_kernel<R, D, DS>), dim3(g.nblocks), dim3(kBlock), 0, s, out, aux, u, g); \
-        else                                                                                                        \
-            hipLaunchKernelGGL((jacdet_fwd_kernel<R, D, DS>), dim3(g.nblocks), dim3(kBlock), 0, s, out, u, g);      \
-    } while (0)
-    if (dim == 3) {
-        if (disp) LAUNCH(3, true); else LAUNCH(3, false);
-    } else {
-        if (disp) LAUNCH(2, true); else LAUNCH(2, false);
-    }
-#undef LAUNCH
+    with_dim(dim, [&](auto DIM) {
+        with_flags([&](auto DISP) {
+            if (backward)
+                hipLaunchKernelGGL((jacdet_bwd_kernel<R, DIM(), DISP()>), dim3(g.nblocks), dim3(kBlock), 0, s, out, aux, u, g);
+            else
+                hipLaunchKernelGGL((jacdet_fwd_kernel<R, DIM(), DISP()>), dim3(g.nblocks), dim3(kBlock), 0, s, out, u, g);
+        }, disp != 0);
+    });
     return finish_launch(s, what);
 }
 

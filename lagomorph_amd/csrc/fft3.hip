@@ -238,18 +238,10 @@ static hipError_t fluid2d_launch(float *out, const float *m, int inverse, const 
     constexpr size_t smem = (size_t)(2 * NY * K::PZ + K::TWN) * sizeof(float2);
     static_assert(smem <= 160 * 1024, "two planes do not fit the LDS");
     const float scale = (float)(1.0 / ((double)NY * (double)NZ));
-    if (inverse) {
-        auto k = fluid2d_kernel<NY, NZ, true>;
-        hipError_t e = allow_smem(k, smem);
-        if (e != hipSuccess) return e;
-        hipLaunchKernelGGL(k, dim3((uint32_t)nn), dim3(K::THREADS), smem, s, out, m, cosX, sinX, cosY, sinY, alpha, beta, gamma, scale, oscale);
-    } else {
-        auto k = fluid2d_kernel<NY, NZ, false>;
-        hipError_t e = allow_smem(k, smem);
-        if (e != hipSuccess) return e;
-        hipLaunchKernelGGL(k, dim3((uint32_t)nn), dim3(K::THREADS), smem, s, out, m, cosX, sinX, cosY, sinY, alpha, beta, gamma, scale, oscale);
-    }
-    return hipSuccess;
+    return with_flags([&](auto INV) {
+        return launch(fluid2d_kernel<NY, NZ, INV()>, dim3((uint32_t)nn), dim3(K::THREADS), smem, s, out, m, cosX, sinX, cosY,
+                      sinY, alpha, beta, gamma, scale, oscale);
+    }, inverse != 0);
 }
 
 int fluid_metric_2d(float *out, const float *m, int inverse, const float *cosX, const float *sinX, const float *cosY,
@@ -314,31 +306,11 @@ static hipError_t zy_launch(const fl::ZYArgs &a, bool inverse, hipStream_t s) {
     constexpr bool kPersist = K::SMEM > 80 * 1024 && K::KV <= 9 && NY < 256 && NZ < 256 && !(NY == 128 && NZ == 192);   // (128, 192: six full slots + the column-0 slot: 16 spilled registers)
     if constexpr (kPersist) if (g_zy_persist) {
         const uint32_t grid = std::min<uint32_t>(a.total, 256u);
-        if (inverse) {
-            auto k = zy_inverse_persist_kernel<NY, NZ>;
-            hipError_t e = allow_smem(k, K::SMEM);
-            if (e != hipSuccess) return e;
-            hipLaunchKernelGGL(k, dim3(grid), dim3(K::THREADS), K::SMEM, s, a);
-        } else {
-            auto k = zy_forward_persist_kernel<NY, NZ>;
-            hipError_t e = allow_smem(k, K::SMEM);
-            if (e != hipSuccess) return e;
-            hipLaunchKernelGGL(k, dim3(grid), dim3(K::THREADS), K::SMEM, s, a);
-        }
-        return hipSuccess;
+        return inverse ? launch(zy_inverse_persist_kernel<NY, NZ>, dim3(grid), dim3(K::THREADS), K::SMEM, s, a)
+                       : launch(zy_forward_persist_kernel<NY, NZ>, dim3(grid), dim3(K::THREADS), K::SMEM, s, a);
     }
-    if (inverse) {
-        auto k = zy_inverse_kernel<NY, NZ>;
-        hipError_t e = allow_smem(k, K::SMEM);
-        if (e != hipSuccess) return e;
-        hipLaunchKernelGGL(k, dim3(a.total), dim3(K::THREADS), K::SMEM, s, a);
-    } else {
-        auto k = zy_forward_kernel<NY, NZ>;
-        hipError_t e = allow_smem(k, K::SMEM);
-        if (e != hipSuccess) return e;
-        hipLaunchKernelGGL(k, dim3(a.total), dim3(K::THREADS), K::SMEM, s, a);
-    }
-    return hipSuccess;
+    return inverse ? launch(zy_inverse_kernel<NY, NZ>, dim3(a.total), dim3(K::THREADS), K::SMEM, s, a)
+                   : launch(zy_forward_kernel<NY, NZ>, dim3(a.total), dim3(K::THREADS), K::SMEM, s, a);
 }
 
 static hipError_t zy_dispatch(int64_t ny, int64_t nz, const fl::ZYArgs &a, bool inverse, hipStream_t s) {

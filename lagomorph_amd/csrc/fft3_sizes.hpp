@@ -50,13 +50,6 @@ template <> struct SzOf<60> { using T = fl::Sz<15, 2>; };
 //    plane's stores to be acknowledged; with the wait in front of the stores the fill finds nothing pending.
 __device__ __forceinline__ void settle(float4 &v) { asm volatile("" : "+v"(v.x), "+v"(v.y), "+v"(v.z), "+v"(v.w)); }
 
-template <typename Kern>
-static hipError_t allow_smem(Kern k, size_t smem) {
-    if (smem <= 64 * 1024) return hipSuccess;
-    return hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize,
-                               (int)smem);
-}
-
 // x lengths of the x pass (fft3x.hip)
 #define LAGO_X_SIZES(X) X(64) X(96) X(128) X(160) X(192) X(256) X(176) X(208) X(112) X(224) X(144) X(240) X(88) X(104) X(120) X(80)
 

@@ -74,34 +74,16 @@ __global__ __launch_bounds__((ypass_threads<NY>())) void ypass_kernel(fl::YArgs 
 template <int NZ>
 static hipError_t zrows_launch(const fl::ZYArgs &a, uint32_t blocks, bool inverse, hipStream_t s) {
     using R = ZRK<NZ>;
-    if (inverse) {
-        auto k = zrows_inverse_kernel<NZ>;
-        hipError_t e = allow_smem(k, R::SMEM);
-        if (e != hipSuccess) return e;
-        hipLaunchKernelGGL(k, dim3(blocks), dim3(R::NT), R::SMEM, s, a.out, a.main_, blocks, a.rev, a.oscale);
-    } else {
-        auto k = zrows_forward_kernel<NZ>;
-        hipError_t e = allow_smem(k, R::SMEM);
-        if (e != hipSuccess) return e;
-        hipLaunchKernelGGL(k, dim3(blocks), dim3(R::NT), R::SMEM, s, a.in, a.main_, blocks, a.rev);
-    }
-    return hipSuccess;
+    return inverse ? launch(zrows_inverse_kernel<NZ>, dim3(blocks), dim3(R::NT), R::SMEM, s, a.out, a.main_, blocks, a.rev,
+                            a.oscale)
+                   : launch(zrows_forward_kernel<NZ>, dim3(blocks), dim3(R::NT), R::SMEM, s, a.in, a.main_, blocks, a.rev);
 }
 template <int NY>
 static hipError_t ypass_launch(const fl::YArgs &a, bool inverse, hipStream_t s) {
     using K = fl::YPass<typename SzOf<NY>::T, ypass_threads<NY>()>;
-    if (inverse) {
-        auto k = ypass_kernel<NY, false>;
-        hipError_t e = allow_smem(k, K::SMEM);
-        if (e != hipSuccess) return e;
-        hipLaunchKernelGGL(k, dim3(a.total), dim3(K::NT), K::SMEM, s, a);
-    } else {
-        auto k = ypass_kernel<NY, true>;
-        hipError_t e = allow_smem(k, K::SMEM);
-        if (e != hipSuccess) return e;
-        hipLaunchKernelGGL(k, dim3(a.total), dim3(K::NT), K::SMEM, s, a);
-    }
-    return hipSuccess;
+    return with_flags([&](auto FWD) {
+        return launch(ypass_kernel<NY, FWD()>, dim3(a.total), dim3(K::NT), K::SMEM, s, a);
+    }, !inverse);
 }
 // the zy transform of planes above the LDS: rows then columns (forward), columns then rows (inverse)
 hipError_t big_zy_dispatch(int64_t nx, int64_t ny, int64_t nz, int64_t nn, const fl::ZYArgs &za, bool inverse, hipStream_t s) {

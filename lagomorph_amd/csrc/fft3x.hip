@@ -100,34 +100,12 @@ static hipError_t xpass2_launch_nt(const fl::XArgs &a, bool inverse, hipStream_t
     // (the persistent kernels exist only for the lengths whose tile fits a CU twice)
     constexpr bool kCanPersist = K0::SMEM * 2 <= 160 * 1024 && (NX <= 160 || NX == 176);
     const bool persist = mode && kCanPersist && (mode >= 2 || pairs >= 8ull * grid) && pairs < (1ull << 32);
-    if (inverse) {
-        using K = fl::XPass<typename SzOf<NX>::T, true, NT>;
-        if constexpr (kCanPersist) if (persist) {
-            auto k = fluid_xpass2_persist_kernel<NX, true, NT>;
-            hipError_t e = allow_smem(k, K::SMEM);
-            if (e != hipSuccess) return e;
-            hipLaunchKernelGGL(k, dim3(grid), dim3(NT), K::SMEM, s, a);
-            return hipSuccess;
-        }
-        auto k = fluid_xpass2_kernel<NX, true, NT>;
-        hipError_t e = allow_smem(k, K::SMEM);
-        if (e != hipSuccess) return e;
-        hipLaunchKernelGGL(k, dim3(a.total), dim3(NT), K::SMEM, s, a);
-    } else {
-        using K = fl::XPass<typename SzOf<NX>::T, false, NT>;
-        if constexpr (kCanPersist) if (persist) {
-            auto k = fluid_xpass2_persist_kernel<NX, false, NT>;
-            hipError_t e = allow_smem(k, K::SMEM);
-            if (e != hipSuccess) return e;
-            hipLaunchKernelGGL(k, dim3(grid), dim3(NT), K::SMEM, s, a);
-            return hipSuccess;
-        }
-        auto k = fluid_xpass2_kernel<NX, false, NT>;
-        hipError_t e = allow_smem(k, K::SMEM);
-        if (e != hipSuccess) return e;
-        hipLaunchKernelGGL(k, dim3(a.total), dim3(NT), K::SMEM, s, a);
-    }
-    return hipSuccess;
+    return with_flags([&](auto INV) {
+        using K = fl::XPass<typename SzOf<NX>::T, INV(), NT>;
+        if constexpr (kCanPersist)
+            if (persist) return launch(fluid_xpass2_persist_kernel<NX, INV(), NT>, dim3(grid), dim3(NT), K::SMEM, s, a);
+        return launch(fluid_xpass2_kernel<NX, INV(), NT>, dim3(a.total), dim3(NT), K::SMEM, s, a);
+    }, inverse);
 }
 
 std::atomic<int> g_xpass_wide{1};

@@ -680,11 +680,8 @@ static BluRef bluestein_table(int N, int M, int sign, hipStream_t s) {
     a.dinner = FastDiv(1u); a.dN = FastDiv((uint32_t)N); a.dL = FastDiv(1u); a.dnhalf = FastDiv((uint32_t)a.nhalf); a.dchunks = FastDiv(1u);
     for (int f = 0, st = 1; f < a.nfac; ++f) { a.ds[f] = FastDiv((uint32_t)st); a.dr[f] = FastDiv((uint32_t)(a.fac[f] + 1) / 2u); st *= a.fac[f]; }
     const size_t smem = (size_t)3 * M * cb;
-    auto k = bluestein_table_kernel<R>;
-    if (smem > 64 * 1024 &&
-        hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) != hipSuccess)
+    if (launch(bluestein_table_kernel<R>, dim3(1), dim3(kBlock), smem, s, reinterpret_cast<GC<R> *>(t->d), a) != hipSuccess)
         return nullptr;   // (~BluTab frees the buffer)
-    hipLaunchKernelGGL(k, dim3(1), dim3(kBlock), smem, s, reinterpret_cast<GC<R> *>(t->d), a);
     if (hipStreamSynchronize(s) != hipSuccess) return nullptr;
     (*g_blu)[key] = t;
     return t;
@@ -762,9 +759,8 @@ static int lines_pass(GC<R> *spec, const R *rin, R *rout, int N, uint64_t inner,
             const uint64_t grid = mode == 0 ? a.chunks : planes * a.chunks;
             if (grid >= (1ull << 31)) return fail_invalid("fluid_metric: bad extent");
             auto k = inpl ? fft_lines_kernel<R, 4, true> : fft_lines_kernel<R, 4>;
-            if (smem > 64 * 1024) LAGO_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
-            hipLaunchKernelGGL(k, dim3((uint32_t)grid), dim3(kBlock), smem, s, spec, rin, rout, a);
-            return LAGO_OK;
+            const hipError_t e = launch(k, dim3((uint32_t)grid), dim3(kBlock), smem, s, spec, rin, rout, a);
+            return e != hipSuccess ? fail_hip(e, "fluid_metric") : LAGO_OK;
         }
     }
     // lines per workgroup: about 1024 points (a radix-4 stage is then one butterfly per thread, and the workgroup's LDS
@@ -821,9 +817,8 @@ static int lines_pass(GC<R> *spec, const R *rin, R *rout, int N, uint64_t inner,
     auto k = a.inplace ? fft_lines_kernel<R, 4, true>
              : pow2    ? fft_lines_kernel<R, 4>
              : (r13 && !odd_small) ? fft_lines_kernel<R, 13> : fft_lines_kernel<R, 7>;
-    if (smem > 64 * 1024) LAGO_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
-    hipLaunchKernelGGL(k, dim3((uint32_t)grid), dim3(kBlock), smem, s, spec, rin, rout, a);
-    return LAGO_OK;
+    const hipError_t e = launch(k, dim3((uint32_t)grid), dim3(kBlock), smem, s, spec, rin, rout, a);
+    return e != hipSuccess ? fail_hip(e, "fluid_metric") : LAGO_OK;
 }
 
 std::atomic<int> g_generic_fuse{1};   // 1 (default): the x pass of the 3D generic path carries the operator (fft_xop_kernel)
@@ -922,26 +917,18 @@ static int xop_pass(GC<R> *spec, int inverse, const R *cosX, const R *sinX, cons
     if (grid >= (1ull << 31)) return 1;
     const size_t smem = inpl ? ldsi(Lc) : lds(Lc);
     a.inplace = inpl ? 1 : 0;
-#define LAGO_XOP_I()                                                                                                 \
-    do {                                                                                                             \
-        auto k = dim == 3 ? (inverse ? fft_xop_kernel<R, 4, true, 3, true> : fft_xop_kernel<R, 4, false, 3, true>)   \
-                          : (inverse ? fft_xop_kernel<R, 4, true, 2, true> : fft_xop_kernel<R, 4, false, 2, true>);  \
-        if (smem > 64 * 1024) LAGO_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem)); \
-        hipLaunchKernelGGL(k, dim3((uint32_t)grid), dim3(kBlock), smem, s, spec, a, o);                              \
-    } while (0)
-#define LAGO_XOP(RM)                                                                                                 \
-    do {                                                                                                             \
-        auto k = dim == 3 ? (inverse ? fft_xop_kernel<R, RM, true, 3> : fft_xop_kernel<R, RM, false, 3>)             \
-                          : (inverse ? fft_xop_kernel<R, RM, true, 2> : fft_xop_kernel<R, RM, false, 2>);            \
-        if (smem > 64 * 1024) LAGO_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem)); \
-        hipLaunchKernelGGL(k, dim3((uint32_t)grid), dim3(kBlock), smem, s, spec, a, o);                              \
-    } while (0)
-    if (pow2 && inpl) LAGO_XOP_I();
-    else if (pow2) LAGO_XOP(4);
-    else if (r13 && !odd_small) LAGO_XOP(13);
-    else LAGO_XOP(7);
-#undef LAGO_XOP
-#undef LAGO_XOP_I
+    const int rmax = pow2 ? 4 : (r13 && !odd_small ? 13 : 7);
+    hipError_t e = hipSuccess;
+    with_dim(dim, [&](auto DIM) {
+        with_flags([&](auto INV, auto INPL) {
+            with_int<4, 7, 13>(rmax, [&](auto RMAX) {
+                if constexpr (!INPL() || RMAX() == 4)   // (in place: power-of-two lines only)
+                    e = launch(fft_xop_kernel<R, RMAX(), INV(), DIM(), INPL()>, dim3((uint32_t)grid), dim3(kBlock), smem, s,
+                               spec, a, o);
+            });
+        }, inverse != 0, pow2 && inpl);
+    });
+    if (e != hipSuccess) return fail_hip(e, "fluid_metric");
     return LAGO_OK;
 }
 

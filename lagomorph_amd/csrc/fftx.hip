@@ -237,12 +237,10 @@ int fluid_coef_launch(float *tab, int inverse, const float *cosX, const float *s
                       double gamma, int64_t nx, int64_t ny, int64_t nzc, int split, hipStream_t s) {
     Geom g;
     if (!make_geom(g, 3, 1, nx, ny, nzc)) return fail_invalid("fluid_coef: bad extent");
-    if (inverse)
-        hipLaunchKernelGGL((fluid_coef_kernel<true>), dim3(g.nblocks), dim3(kBlock), 0, s, tab, cosX, sinX, cosY, sinY,
+    with_flags([&](auto INV) {
+        hipLaunchKernelGGL((fluid_coef_kernel<INV()>), dim3(g.nblocks), dim3(kBlock), 0, s, tab, cosX, sinX, cosY, sinY,
                            cosZ, sinZ, alpha, beta, gamma, g, split);
-    else
-        hipLaunchKernelGGL((fluid_coef_kernel<false>), dim3(g.nblocks), dim3(kBlock), 0, s, tab, cosX, sinX, cosY, sinY,
-                           cosZ, sinZ, alpha, beta, gamma, g, split);
+    }, inverse != 0);
     return finish_launch(s, "fluid_coef");
 }
 
@@ -265,20 +263,10 @@ static hipError_t xpass_launch(float2 *F, const float *tab, int inverse, int64_t
     const size_t smem = (size_t)(3 * NX * (kKL + 1) + NX / 2) * sizeof(float2);
     const uint64_t total = (uint64_t)nn * ny * nchunks;
     if (total >= (1ull << 31)) return hipErrorInvalidValue;
-    auto kinv = fluid_xpass_kernel<LOGN, true>;
-    auto kfwd = fluid_xpass_kernel<LOGN, false>;
-    if (smem > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(inverse ? kinv : kfwd),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-        if (e != hipSuccess) return e;
-    }
-    if (inverse)
-        hipLaunchKernelGGL(kinv, dim3((uint32_t)total), dim3(256), smem, s, F, tab, (int)ny, (int)nzc, KC, nchunks, scale,
-                           (uint32_t)total, LAGO_XPASS_DBG);
-    else
-        hipLaunchKernelGGL(kfwd, dim3((uint32_t)total), dim3(256), smem, s, F, tab, (int)ny, (int)nzc, KC, nchunks, scale,
-                           (uint32_t)total, LAGO_XPASS_DBG);
-    return hipSuccess;
+    return with_flags([&](auto INV) {
+        return launch(fluid_xpass_kernel<LOGN, INV()>, dim3((uint32_t)total), dim3(256), smem, s, F, tab, (int)ny, (int)nzc,
+                      KC, nchunks, scale, (uint32_t)total, LAGO_XPASS_DBG);
+    }, inverse != 0);
 }
 
 int fluid_xpass_launch(float *F, const float *tab, int inverse, int64_t nn, int64_t nx, int64_t ny, int64_t nzc,

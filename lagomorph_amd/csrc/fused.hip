@@ -242,41 +242,38 @@ std::atomic<int> g_tile_cube{1};      // 1: 128^3 / 160^3 volumes take the insta
 // makes the gather kernels of the Euler step ask for at least that much LDS, so that only one of their workgroups fits a
 // CU and the FFT passes of ANOTHER stream can co-reside (measured: 30 % slower, profiles/r04_stream_split.md).  The
 // product library reads no environment variable here.
-template <typename K>
-static size_t padded_smem(K k, size_t smem) {
+// (lago::launch allows the kernel the padded size when it is above 64 KB)
+static size_t padded_smem(size_t smem) {
 #ifdef LAGO_PROFILING
     static const size_t pad = [] {
         const char *e = getenv("LAGO_EXP_GATHER_PAD");
         return e ? (size_t)strtoul(e, nullptr, 10) : (size_t)0;
     }();
-    if (pad > smem) {
-        smem = pad;
-        if (smem > 64 * 1024) (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-    }
-#else
-    (void)k;
+    if (pad > smem) smem = pad;
 #endif
     return smem;
 }
 
+// returns 1 when the shape is left to the other kernels
 template <typename R>
-static bool compose_window_launch(R *out, const R *u, const R *v, double ds, double dt, const Geom &g, int64_t nn,
-                                  hipStream_t s) {
+static int compose_window_launch(R *out, const R *u, const R *v, double ds, double dt, const Geom &g, int64_t nn,
+                                 hipStream_t s) {
     if constexpr (sizeof(R) == 4) {
         GWGrid w;
-        if (!make_gwgrid(w, g, nn) || ((uintptr_t)v & 15u)) return false;
+        if (!make_gwgrid(w, g, nn) || ((uintptr_t)v & 15u)) return 1;
         constexpr int NT = GW::NT, U = 8;
         const size_t smem = GW::lds_bytes<NT>();
         // (compiling the geometry of 128^3 / 160^3 volumes in, as ad_star3_tile_kernel does, costs this kernel 2-15
         // spilled registers at its 128: not done)
-        if (unit_dt<R>(ds))
-            hipLaunchKernelGGL((compose3_window_kernel<NT, U, true>), dim3(w.total), dim3(NT), padded_smem(compose3_window_kernel<NT, U, true>, smem), s, out, u, v, ds, dt, g, w);
-        else
-            hipLaunchKernelGGL((compose3_window_kernel<NT, U, false>), dim3(w.total), dim3(NT), padded_smem(compose3_window_kernel<NT, U, false>, smem), s, out, u, v, ds, dt, g, w);
+        const hipError_t e = with_flags([&](auto UNIT) {
+            return launch(compose3_window_kernel<NT, U, UNIT()>, dim3(w.total), dim3(NT), padded_smem(smem), s, out, u, v,
+                          ds, dt, g, w);
+        }, unit_dt<R>(ds));
+        if (e != hipSuccess) return fail_hip(e, "compose");
         note_path(LP_GATHER_WINDOW);
-        return true;
+        return LAGO_OK;
     }
-    return false;
+    return 1;
 }
 
 template <typename R>
@@ -289,26 +286,22 @@ static int compose_impl(R *out, const R *u, const R *v, double ds, double dt, in
     if (!out || !u || !v) return fail_invalid("compose: null pointer");
     hipStream_t s = (hipStream_t)stream;
     constexpr int U = 2;
-    if (dim == 3 && g_interp_vec && g_gather_window && g.nvox >= 32768u && compose_window_launch(out, u, v, ds, dt, g, nn, s))
-        return finish_launch(s, "compose");
-    if (dim == 3 && g_interp_vec && g.nz >= 2 && kBlock / g.nz + 1 < g.ny && g.nvox >= 4u * U * kBlock) {
-        const uint32_t nbx_u = (g.nvox + U * kBlock - 1) / (U * kBlock);
-        const uint64_t nb = (uint64_t)nbx_u * (uint64_t)nn;
-        if (nb < (1ull << 31)) {
-            if (unit_dt<R>(ds))
-                hipLaunchKernelGGL((compose3_unroll_kernel<R, U, true>), dim3((uint32_t)nb), dim3(kBlock), 0, s, out, u, v,
-                                   ds, dt, g, nbx_u, (uint32_t)nb);
-            else
-                hipLaunchKernelGGL((compose3_unroll_kernel<R, U, false>), dim3((uint32_t)nb), dim3(kBlock), 0, s, out, u, v,
-                                   ds, dt, g, nbx_u, (uint32_t)nb);
-            note_path(LP_VECTOR_GATHER);
-            return finish_launch(s, "compose");
-        }
+    if (dim == 3 && g_interp_vec && g_gather_window && g.nvox >= 32768u) {
+        const int rc = compose_window_launch(out, u, v, ds, dt, g, nn, s);
+        if (rc != 1) return rc != LAGO_OK ? rc : finish_launch(s, "compose");
     }
-    if (dim == 3)
-        hipLaunchKernelGGL((compose_kernel<R, 3>), dim3(g.nblocks), dim3(kBlock), 0, s, out, u, v, ds, dt, g);
-    else
-        hipLaunchKernelGGL((compose_kernel<R, 2>), dim3(g.nblocks), dim3(kBlock), 0, s, out, u, v, ds, dt, g);
+    uint32_t nbx_u, nb;
+    if (dim == 3 && g_interp_vec && slab_grid(g, nn, U, nbx_u, nb)) {
+        with_flags([&](auto UNIT) {
+            hipLaunchKernelGGL((compose3_unroll_kernel<R, U, UNIT()>), dim3(nb), dim3(kBlock), 0, s, out, u, v, ds, dt, g,
+                               nbx_u, nb);
+        }, unit_dt<R>(ds));
+        note_path(LP_VECTOR_GATHER);
+        return finish_launch(s, "compose");
+    }
+    with_dim(dim, [&](auto DIM) {
+        hipLaunchKernelGGL((compose_kernel<R, DIM()>), dim3(g.nblocks), dim3(kBlock), 0, s, out, u, v, ds, dt, g);
+    });
     return finish_launch(s, "compose");
 }
 
@@ -596,37 +589,36 @@ std::atomic<int> g_stencil_tile{1};  // 1: LDS row-tile stencil kernels where th
 // workgroups per CU).  Measured against 256 x 2 (2 x 2 rows), 1024 x 2 (4 x 4), 768 x 2, 256 x 4 and 512 x 4 voxels
 // per thread, halo rows by LDS-direct loads, streaming stores and an earlier issue of the first gathers: all within
 // +-3 % or slower (profiles/r03_stencil_tile.md).
+// returns 1 when the shape is left to the other kernels
 template <typename R>
-static bool ad_star_tile_launch(R *out, R *mphi, const R *phi, const R *m, const Geom &g, int64_t nn, hipStream_t s) {
+static int ad_star_tile_launch(R *out, R *mphi, const R *phi, const R *m, const Geom &g, int64_t nn, hipStream_t s) {
     constexpr int NT = 512, U = 2, RI = 5;
     RowTile t;
     size_t smem;
-    if (!make_row_tile(t, g, nn, NT * U, NT, 3, (int)sizeof(R), RI, smem)) return false;
-    const int zc = (g.nz + 63) / 64;
-#define LAGO_ADT(ZC)                                                                                               \
-    hipLaunchKernelGGL((ad_star3_tile_kernel<R, NT, U, RI, ZC>), dim3(t.total), dim3(NT), smem, s, out, mphi, phi, m, g, t)
+    if (!make_row_tile(t, g, nn, NT * U, NT, 3, (int)sizeof(R), RI, smem)) return 1;
     if constexpr (sizeof(R) == 4) {
         // the two benchmark volumes with their geometry compiled in
         const bool cube = g.nx == g.ny && g.ny == g.nz && t.TX == 2 && g_tile_cube;
         if (cube && g.nz == 128 && t.TY == 4) {
-            hipLaunchKernelGGL((ad_star3_tile_kernel<R, NT, U, RI, 2, 128>), dim3(t.total), dim3(NT), padded_smem(ad_star3_tile_kernel<R, NT, U, RI, 2, 128>, smem), s, out, mphi, phi, m, g, t);
+            const hipError_t e = launch(ad_star3_tile_kernel<R, NT, U, RI, 2, 128>, dim3(t.total), dim3(NT),
+                                        padded_smem(smem), s, out, mphi, phi, m, g, t);
+            if (e != hipSuccess) return fail_hip(e, "ad_star");
             note_path(LP_STENCIL_TILE);
-            return true;
+            return LAGO_OK;
         }
         if (cube && g.nz == 160 && t.TY == 3) {
             hipLaunchKernelGGL((ad_star3_tile_kernel<R, NT, U, RI, 3, 160>), dim3(t.total), dim3(NT), smem, s, out, mphi, phi, m, g, t);
             note_path(LP_STENCIL_TILE);
-            return true;
+            return LAGO_OK;
         }
     }
-    if (zc == 1) LAGO_ADT(1);
-    else if (zc == 2) LAGO_ADT(2);
-    else if (zc == 3) LAGO_ADT(3);
-    else if (zc == 4) LAGO_ADT(4);
-    else return false;
-#undef LAGO_ADT
+    if (!with_int<1, 2, 3, 4>((g.nz + 63) / 64, [&](auto ZC) {
+            hipLaunchKernelGGL((ad_star3_tile_kernel<R, NT, U, RI, ZC()>), dim3(t.total), dim3(NT), smem, s, out, mphi, phi,
+                               m, g, t);
+        }))
+        return 1;
     note_path(LP_STENCIL_TILE);
-    return true;
+    return LAGO_OK;
 }
 
 template <typename R>
@@ -639,26 +631,23 @@ static int ad_star_impl(R *out, R *mphi, const R *phi, const R *m, int dim, int6
     if (!out || !phi || !m) return fail_invalid("ad_star: null pointer");
     if (out == phi || out == m || (mphi && (mphi == phi || mphi == m || mphi == out)))
         return fail_invalid("ad_star: outputs may not alias an input or each other");
-    if (nx <= 1 || ny <= 1 || (dim == 3 && nz <= 1))
+    if (thin(dim, nx, ny, nz))
         return fail_invalid("Jacobian times vectorfield not implemented for 'thin' dimensions");
     hipStream_t s = (hipStream_t)stream;
     constexpr int U = 2;
-    if (dim == 3 && g_interp_vec && g_stencil_tile && g.nvox >= 4096u && ad_star_tile_launch<R>(out, mphi, phi, m, g, nn, s))
-        return finish_launch(s, "ad_star");
-    if (dim == 3 && g_interp_vec && g.nz >= 2 && kBlock / g.nz + 1 < g.ny && g.nvox >= 4u * U * kBlock) {
-        const uint32_t nbx_u = (g.nvox + U * kBlock - 1) / (U * kBlock);
-        const uint64_t nb = (uint64_t)nbx_u * (uint64_t)nn;
-        if (nb < (1ull << 31)) {
-            hipLaunchKernelGGL((ad_star3_unroll_kernel<R, U>), dim3((uint32_t)nb), dim3(kBlock), 0, s, out, mphi, phi, m, g,
-                               nbx_u, (uint32_t)nb);
-            note_path(LP_VECTOR_GATHER);
-            return finish_launch(s, "ad_star");
-        }
+    if (dim == 3 && g_interp_vec && g_stencil_tile && g.nvox >= 4096u) {
+        const int rc = ad_star_tile_launch<R>(out, mphi, phi, m, g, nn, s);
+        if (rc != 1) return rc != LAGO_OK ? rc : finish_launch(s, "ad_star");
     }
-    if (dim == 3)
-        hipLaunchKernelGGL((ad_star_kernel<R, 3>), dim3(g.nblocks), dim3(kBlock), 0, s, out, mphi, phi, m, g);
-    else
-        hipLaunchKernelGGL((ad_star_kernel<R, 2>), dim3(g.nblocks), dim3(kBlock), 0, s, out, mphi, phi, m, g);
+    uint32_t nbx_u, nb;
+    if (dim == 3 && g_interp_vec && slab_grid(g, nn, U, nbx_u, nb)) {
+        hipLaunchKernelGGL((ad_star3_unroll_kernel<R, U>), dim3(nb), dim3(kBlock), 0, s, out, mphi, phi, m, g, nbx_u, nb);
+        note_path(LP_VECTOR_GATHER);
+        return finish_launch(s, "ad_star");
+    }
+    with_dim(dim, [&](auto DIM) {
+        hipLaunchKernelGGL((ad_star_kernel<R, DIM()>), dim3(g.nblocks), dim3(kBlock), 0, s, out, mphi, phi, m, g);
+    });
     return finish_launch(s, "ad_star");
 }
 
@@ -702,15 +691,13 @@ int lincomb_impl(R *out, int k, const R *x0, const R *x1, const R *x2, const R *
     const size_t nvec = vec ? (size_t)n / VEC : (size_t)n;
     const uint32_t grid = (uint32_t)std::min<size_t>((nvec + 255) / 256, (size_t)256 * 32);
     const int rev = next_direction();
-#define LAGO_LC(K, V)                                                                                              \
-    hipLaunchKernelGGL((lincomb_kernel<R, K, V>), dim3(grid), dim3(256), 0, s, out, x0, x1, x2, x3, (R)c0, (R)c1, (R)c2, \
-                       (R)c3, nvec, rev)
-    if (vec) {
-        if (k == 1) LAGO_LC(1, VEC); else if (k == 2) LAGO_LC(2, VEC); else if (k == 3) LAGO_LC(3, VEC); else LAGO_LC(4, VEC);
-    } else {
-        if (k == 1) LAGO_LC(1, 1); else if (k == 2) LAGO_LC(2, 1); else if (k == 3) LAGO_LC(3, 1); else LAGO_LC(4, 1);
-    }
-#undef LAGO_LC
+    with_flags([&](auto WIDE) {
+        constexpr int V = WIDE() ? VEC : 1;
+        with_int<1, 2, 3, 4>(k, [&](auto K) {
+            hipLaunchKernelGGL((lincomb_kernel<R, K(), V>), dim3(grid), dim3(256), 0, s, out, x0, x1, x2, x3, (R)c0, (R)c1,
+                               (R)c2, (R)c3, nvec, rev);
+        });
+    }, vec);
     return finish_launch(s, "lincomb");
 }
 

@@ -244,11 +244,6 @@ __global__ __launch_bounds__(kBlock) void gauss_s_kernel(R *out, const R *in, Ga
     }
 }
 
-static bool gauss_overlaps(const void *a, const void *b, size_t bytes) {
-    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-    return x < y + bytes && y < x + bytes;
-}
-
 template <typename R>
 static bool gauss_plan(GaussPass &p, int axis, int r, int mode, int64_t rows, const Geom &g, const R *out) {
     const int64_t ext[3] = {g.nx, g.ny, g.nz};
@@ -333,7 +328,7 @@ static int gauss_impl(R *out, const R *in, R *scratch, const int *radii, const d
     if (g.nblocks == 0) return LAGO_OK;
     if (!out || !in) return fail_invalid("gaussian_smooth: null pointer");
     const size_t bytes = (size_t)rows * g.nvox * sizeof(R);
-    if (gauss_overlaps(out, in, bytes)) return fail_invalid("gaussian_smooth: out must not alias in");
+    if (overlaps(out, in, bytes)) return fail_invalid("gaussian_smooth: out must not alias in");
 
     // the passes, outermost axis first.  Three passes that accumulate onto `out` cannot use it as a stage: the middle
     // one runs in place on the scratch tensor, which needs a pass that stages whole lines (see the head of this file);
@@ -369,7 +364,7 @@ static int gauss_impl(R *out, const R *in, R *scratch, const int *radii, const d
     }
     if (m >= 2) {
         if (!scratch) return fail_invalid("gaussian_smooth: two or more passes need the scratch tensor");
-        if (gauss_overlaps(scratch, in, bytes) || gauss_overlaps(scratch, out, bytes))
+        if (overlaps(scratch, in, bytes) || overlaps(scratch, out, bytes))
             return fail_invalid("gaussian_smooth: scratch must not alias in or out");
     }
     // pass.vec was planned against `out`; the scratch tensor must allow the same stores

@@ -225,11 +225,10 @@ static bool interp_window_launch(R *out, const R *I, const R *u, double dt, int 
         constexpr int NT = GW::NT, U = 8;
         const size_t smem = GW::lds_bytes<NT>();
         const bool unit = unit_dt<R>(dt);
-#define LAGO_IW(UN, B) \
-    hipLaunchKernelGGL((interp3_window_kernel<NT, U, UN, B>), dim3(w.total), dim3(NT), smem, s, out, I, u, dt, nc, g, w)
-        if (unit) { if (bc) LAGO_IW(true, true); else LAGO_IW(true, false); }
-        else { if (bc) LAGO_IW(false, true); else LAGO_IW(false, false); }
-#undef LAGO_IW
+        with_flags([&](auto UNIT, auto BC) {
+            hipLaunchKernelGGL((interp3_window_kernel<NT, U, UNIT(), BC()>), dim3(w.total), dim3(NT), smem, s, out, I, u,
+                               dt, nc, g, w);
+        }, unit, bc);
         note_path(LP_GATHER_WINDOW);
         return true;
     }
@@ -474,11 +473,10 @@ static bool interp_backward_2d_lds(R *d_I, R *d_u, const R *go, const R *I, cons
     sg.d_tiles = FastDiv(sg.tiles_per_item);
     sg.d_tw = FastDiv(sg.ntw);
     const size_t smem = (size_t)sg.WH * sg.WW * sizeof(double);
-#define LAGO_S2(B, NU) \
-    hipLaunchKernelGGL((splat2d_lds_kernel<R, B, NU>), dim3(sg.total), dim3(kS2T), smem, s, d_I, d_u, go, I, u, dt, nc, sg, umode, (R)addgo)
-    if (bc) { if (need_u) LAGO_S2(true, true); else LAGO_S2(true, false); }
-    else { if (need_u) LAGO_S2(false, true); else LAGO_S2(false, false); }
-#undef LAGO_S2
+    with_flags([&](auto BC, auto NEED_U) {
+        hipLaunchKernelGGL((splat2d_lds_kernel<R, BC(), NEED_U()>), dim3(sg.total), dim3(kS2T), smem, s, d_I, d_u, go, I,
+                           u, dt, nc, sg, umode, (R)addgo);
+    }, bc, need_u);
     note_path(LP_SPLAT_2D);
     return true;
 }
@@ -524,45 +522,22 @@ static int interp_forward_impl(R *out, const R *I, const R *u, double dt, int di
     if (dim == 3 && g_interp_vec && g_gather_window && nc >= 2 && g.nvox >= 32768u &&
         interp_window_launch<R>(out, I, u, dt, (int)nc, bc != 0, g, nn, s))
         return finish_launch(s, "interp_forward");
-    if (dim == 3 && g_interp_vec && g.nz >= 2 && kBlock / g.nz + 1 < g.ny && g.nvox >= 4u * U * kBlock) {
-        const uint32_t nbx_u = (g.nvox + U * kBlock - 1) / (U * kBlock);
-        const uint64_t nb = (uint64_t)nbx_u * (uint64_t)nn;
-        if (nb < (1ull << 31)) {
-#define LAUNCH_U(B, UN)                                                                                              \
-    hipLaunchKernelGGL((interp_fwd3_unroll_kernel<R, B, U, UN>), dim3((uint32_t)nb), dim3(kBlock), 0, s, out, I, u, dt, \
-                       (int)nc, g, nbx_u, (uint32_t)nb)
-            const bool unit = unit_dt<R>(dt);
-            if (bc) {
-                if (unit) LAUNCH_U(true, true); else LAUNCH_U(true, false);
-            } else {
-                if (unit) LAUNCH_U(false, true); else LAUNCH_U(false, false);
-            }
-#undef LAUNCH_U
-            note_path(LP_VECTOR_GATHER);
-            return finish_launch(s, "interp_forward");
-        }
+    uint32_t nbx_u, nb;
+    if (dim == 3 && g_interp_vec && slab_grid(g, nn, U, nbx_u, nb)) {
+        with_flags([&](auto BC, auto UNIT) {
+            hipLaunchKernelGGL((interp_fwd3_unroll_kernel<R, BC(), U, UNIT()>), dim3(nb), dim3(kBlock), 0, s, out, I, u,
+                               dt, (int)nc, g, nbx_u, nb);
+        }, bc != 0, unit_dt<R>(dt));
+        note_path(LP_VECTOR_GATHER);
+        return finish_launch(s, "interp_forward");
     }
-#define LAUNCH(D, B) \
-    hipLaunchKernelGGL((interp_fwd_kernel<R, D, B>), dim3(g.nblocks), dim3(kBlock), 0, s, out, I, u, dt, (int)nc, g)
-    if (dim == 3) {
-        if (bc) LAUNCH(3, true); else LAUNCH(3, false);
-    } else {
-        if (bc) LAUNCH(2, true); else LAUNCH(2, false);
-    }
-#undef LAUNCH
+    with_dim(dim, [&](auto DIM) {
+        with_flags([&](auto BC) {
+            hipLaunchKernelGGL((interp_fwd_kernel<R, DIM(), BC()>), dim3(g.nblocks), dim3(kBlock), 0, s, out, I, u, dt,
+                               (int)nc, g);
+        }, bc != 0);
+    });
     return finish_launch(s, "interp_forward");
-}
-
-template <typename R, int DIM, bool BC>
-static void launch_bwd(R *d_I, R *d_u, const R *go, const R *I, const R *u, double dt, int nc, const Geom &g,
-                       bool need_I, bool need_u, int umode, double addgo, hipStream_t s) {
-#define LAUNCH(NI, NU)                                                                                          \
-    hipLaunchKernelGGL((interp_bwd_kernel<R, DIM, BC, NI, NU>), dim3(g.nblocks), dim3(kBlock), 0, s, d_I, d_u, \
-                       go, I, u, dt, nc, g, umode, (R)addgo)
-    if (need_I && need_u) LAUNCH(true, true);
-    else if (need_I) LAUNCH(true, false);
-    else if (need_u) LAUNCH(false, true);
-#undef LAUNCH
 }
 
 template <typename R>
@@ -602,13 +577,13 @@ static int interp_backward_impl(R *d_I, R *d_u, const R *go, const R *I, const R
         interp_backward_2d_lds<R>(d_I, d_u, go, I, u, dt, (int)nc, nn, g, bc != 0, need_u != 0, umode, addgo, s))
         return finish_launch(s, "interp_backward");
     note_path(LP_SPLAT_GLOBAL);
-    if (dim == 3) {
-        if (bc) launch_bwd<R, 3, true>(d_I, d_u, go, I, u, dt, (int)nc, g, need_I, need_u, umode, addgo, s);
-        else launch_bwd<R, 3, false>(d_I, d_u, go, I, u, dt, (int)nc, g, need_I, need_u, umode, addgo, s);
-    } else {
-        if (bc) launch_bwd<R, 2, true>(d_I, d_u, go, I, u, dt, (int)nc, g, need_I, need_u, umode, addgo, s);
-        else launch_bwd<R, 2, false>(d_I, d_u, go, I, u, dt, (int)nc, g, need_I, need_u, umode, addgo, s);
-    }
+    with_dim(dim, [&](auto DIM) {
+        with_flags([&](auto BC, auto NEED_I, auto NEED_U) {
+            if constexpr (NEED_I() || NEED_U())   // (neither: returned above, and no such kernel exists)
+                hipLaunchKernelGGL((interp_bwd_kernel<R, DIM(), BC(), NEED_I(), NEED_U()>), dim3(g.nblocks), dim3(kBlock),
+                                   0, s, d_I, d_u, go, I, u, dt, (int)nc, g, umode, (R)addgo);
+        }, bc != 0, need_I != 0, need_u != 0);
+    });
     return finish_launch(s, "interp_backward");
 }
 

@@ -129,11 +129,6 @@ __global__ __launch_bounds__(kBlock) void invert_disp_adjoint_kernel(R *__restri
     }
 }
 
-static bool overlaps(const void *a, const void *b, size_t bytes) {
-    const uintptr_t p = (uintptr_t)a, q = (uintptr_t)b;
-    return p < q + bytes && q < p + bytes;
-}
-
 template <typename R>
 static int invert_forward_impl(R *out, const R *u, int iters, int dim, int64_t nn, int64_t nx, int64_t ny, int64_t nz,
                                void *stream) {
@@ -147,10 +142,9 @@ static int invert_forward_impl(R *out, const R *u, int iters, int dim, int64_t n
     if (overlaps(out, u, (size_t)nn * dim * g.nvox * sizeof(R)))
         return fail_invalid("invert_displacement_forward: out must not alias u");
     hipStream_t s = (hipStream_t)stream;
-    if (dim == 3)
-        hipLaunchKernelGGL((invert_disp_kernel<R, 3>), dim3(g.nblocks), dim3(kBlock), 0, s, out, u, iters, g);
-    else
-        hipLaunchKernelGGL((invert_disp_kernel<R, 2>), dim3(g.nblocks), dim3(kBlock), 0, s, out, u, iters, g);
+    with_dim(dim, [&](auto DIM) {
+        hipLaunchKernelGGL((invert_disp_kernel<R, DIM()>), dim3(g.nblocks), dim3(kBlock), 0, s, out, u, iters, g);
+    });
     return finish_launch(s, "invert_displacement_forward");
 }
 
@@ -166,10 +160,9 @@ static int invert_adjoint_impl(R *lam, const R *go, const R *u, const R *v, int 
     if (overlaps(lam, u, bytes) || overlaps(lam, v, bytes) || overlaps(lam, go, bytes))
         return fail_invalid("invert_displacement_adjoint: lam must not alias an input");
     hipStream_t s = (hipStream_t)stream;
-    if (dim == 3)
-        hipLaunchKernelGGL((invert_disp_adjoint_kernel<R, 3>), dim3(g.nblocks), dim3(kBlock), 0, s, lam, go, u, v, g);
-    else
-        hipLaunchKernelGGL((invert_disp_adjoint_kernel<R, 2>), dim3(g.nblocks), dim3(kBlock), 0, s, lam, go, u, v, g);
+    with_dim(dim, [&](auto DIM) {
+        hipLaunchKernelGGL((invert_disp_adjoint_kernel<R, DIM()>), dim3(g.nblocks), dim3(kBlock), 0, s, lam, go, u, v, g);
+    });
     return finish_launch(s, "invert_displacement_adjoint");
 }
 

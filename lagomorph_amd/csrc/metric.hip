@@ -80,15 +80,12 @@ int fluid_operator_impl(R *Fm, int inverse, const R *cosX, const R *sinX, const 
     if (((uintptr_t)Fm) % (2 * sizeof(R))) return fail_invalid("fluid_operator: Fmv must be aligned to a complex element");
     hipStream_t s = (hipStream_t)stream;
     Cplx<R> *F = reinterpret_cast<Cplx<R> *>(Fm);
-#define LAUNCH(D, INV)                                                                                           \
-    hipLaunchKernelGGL((fluid_kernel<R, D, INV>), dim3(g.nblocks), dim3(kBlock), 0, s, F, cosX, sinX, cosY, sinY, \
-                       cosZ, sinZ, alpha, beta, gamma, (int)nn, g, (R)scale)
-    if (dim == 3) {
-        if (inverse) LAUNCH(3, true); else LAUNCH(3, false);
-    } else {
-        if (inverse) LAUNCH(2, true); else LAUNCH(2, false);
-    }
-#undef LAUNCH
+    with_dim(dim, [&](auto DIM) {
+        with_flags([&](auto INV) {
+            hipLaunchKernelGGL((fluid_kernel<R, DIM(), INV()>), dim3(g.nblocks), dim3(kBlock), 0, s, F, cosX, sinX, cosY,
+                               sinY, cosZ, sinZ, alpha, beta, gamma, (int)nn, g, (R)scale);
+        }, inverse != 0);
+    });
     return finish_launch(s, "fluid_operator");
 }
 

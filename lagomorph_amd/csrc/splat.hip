@@ -971,37 +971,6 @@ static bool make_shear(ShearGeom &sg, const Geom &g, int64_t nn, size_t &smem, i
     return true;
 }
 
-template <int NT>
-static hipError_t launch_shear(float *d_I, float *d_u, const float *go, const float *I, const float *u, double dt, int nc,
-                               const ShearGeom &sg, size_t smem, bool bc, bool need_u, int umode, float addgo, hipStream_t s) {
-    const bool unit = unit_dt<float>(dt);
-    // several channels with d_u wanted: keep d_u in registers when the workgroup covers the tile in at most 4 passes
-    const int passes = (int)((sg.tile_vox + NT - 1) / NT);
-    const bool mc = need_u && nc > 1 && passes <= 4 && g_shear_mc;
-#define LAGO_SHEAR(NU, UN, B)                                                                                     \
-    do {                                                                                                          \
-        auto k = !mc ? splat_shear_kernel<NT, NU, UN, B, 0>                                                       \
-                     : (passes <= 1 ? splat_shear_kernel<NT, NU, UN, B, (NU ? 1 : 0)>                             \
-                        : passes <= 2 ? splat_shear_kernel<NT, NU, UN, B, (NU ? 2 : 0)>                           \
-                                      : splat_shear_kernel<NT, NU, UN, B, (NU ? 4 : 0)>);                         \
-        if (smem > 64 * 1024) {                                                                                   \
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(k),                                 \
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);            \
-            if (e != hipSuccess) return e;                                                                        \
-        }                                                                                                         \
-        hipLaunchKernelGGL(k, dim3(sg.total), dim3(NT), smem, s, d_I, d_u, go, I, u, dt, nc, sg, umode, addgo);   \
-    } while (0)
-    if (need_u) {
-        if (unit) { if (bc) LAGO_SHEAR(true, true, true); else LAGO_SHEAR(true, true, false); }
-        else { if (bc) LAGO_SHEAR(true, false, true); else LAGO_SHEAR(true, false, false); }
-    } else {
-        if (unit) { if (bc) LAGO_SHEAR(false, true, true); else LAGO_SHEAR(false, true, false); }
-        else { if (bc) LAGO_SHEAR(false, false, true); else LAGO_SHEAR(false, false, false); }
-    }
-#undef LAGO_SHEAR
-    return hipSuccess;
-}
-
 // float32 displacement splat through the sheared-window kernel; returns 1 when the shape is left to the
 // general tiled kernel.
 static int interp_backward_shear(float *d_I, float *d_u, const float *go, const float *I, const float *u, double dt,
@@ -1009,35 +978,38 @@ static int interp_backward_shear(float *d_I, float *d_u, const float *go, const 
     if (!g_shear_on) return 1;
     ShearGeom sg;
     size_t smem;
-    hipError_t e;
+    hipError_t e = hipErrorInvalidValue;   // (every dispatch below assigns it)
     const int shear_nt = g_shear_nt;
     // the geometry-once kernel: in isolation it gains 7-12 % for non-unit steps and measures within +-3 % for dt = +-1
     // (smaller tiles flush more cells); inside lddmm_step -- running d_u / d_I sums, 3-voxel displacements -- it wins
     // for both: 21.63 -> 20.40 ms per step at 8 x 160^3, 10.27 -> 9.85 at 8 x 128^3 (tools/ab_step_mc.py)
     const bool unit_step = unit_dt<float>(dt);
     if (need_u && nc > 1 && g_shear_mc >= 2 && shear_nt >= 1024 && make_shear(sg, g, nn, smem, 2048)) {
-        const bool unit = unit_step;
-        const bool one = sg.tile_vox <= 1024u;
-#define LAGO_SHEAR_MC(UN, B)                                                                                      \
-    do {                                                                                                          \
-        auto k = one ? splat_shear_mc_kernel<1024, UN, B, 1> : splat_shear_mc_kernel<1024, UN, B, 2>;             \
-        if (smem > 64 * 1024) {                                                                                   \
-            e = hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, \
-                                    (int)smem);                                                                   \
-            if (e != hipSuccess) return fail_hip(e, "interp_backward (sheared-window splat)");                    \
-        }                                                                                                         \
-        hipLaunchKernelGGL(k, dim3(sg.total), dim3(1024), smem, s, d_I, d_u, go, I, u, dt, nc, sg, umode, addgo);  \
-    } while (0)
-        if (unit) { if (bc) LAGO_SHEAR_MC(true, true); else LAGO_SHEAR_MC(true, false); }
-        else { if (bc) LAGO_SHEAR_MC(false, true); else LAGO_SHEAR_MC(false, false); }
-#undef LAGO_SHEAR_MC
+        with_flags([&](auto UNIT, auto BC) {
+            with_int<1, 2>(sg.tile_vox <= 1024u ? 1 : 2, [&](auto VPL) {
+                e = launch(splat_shear_mc_kernel<1024, UNIT(), BC(), VPL()>, dim3(sg.total), dim3(1024), smem, s, d_I, d_u,
+                           go, I, u, dt, nc, sg, umode, addgo);
+            });
+        }, unit_step, bc);
+        if (e != hipSuccess) return fail_hip(e, "interp_backward (sheared-window splat)");
         note_path(LP_SPLAT_SHEAR_MC);
         return finish_launch(s, "interp_backward (sheared-window splat)");
     }
     if (!make_shear(sg, g, nn, smem)) return 1;
-    if (shear_nt >= 1024) e = launch_shear<1024>(d_I, d_u, go, I, u, dt, nc, sg, smem, bc, need_u, umode, addgo, s);
-    else if (shear_nt >= 512) e = launch_shear<512>(d_I, d_u, go, I, u, dt, nc, sg, smem, bc, need_u, umode, addgo, s);
-    else e = launch_shear<256>(d_I, d_u, go, I, u, dt, nc, sg, smem, bc, need_u, umode, addgo, s);
+    const int nt = shear_nt >= 1024 ? 1024 : (shear_nt >= 512 ? 512 : 256);
+    // several channels with d_u wanted: keep d_u in registers when the workgroup covers the tile in at most 4 passes
+    const int passes = (int)((sg.tile_vox + nt - 1) / nt);
+    const bool mc = need_u && nc > 1 && passes <= 4 && g_shear_mc;
+    const int vpl = !mc ? 0 : (passes <= 1 ? 1 : (passes <= 2 ? 2 : 4));
+    with_int<256, 512, 1024>(nt, [&](auto NT) {
+        with_flags([&](auto NEED_U, auto UNIT, auto BC) {
+            with_int<0, 1, 2, 4>(vpl, [&](auto VPL) {
+                if constexpr (NEED_U() || VPL() == 0)   // (mc implies need_u: no other instantiation exists)
+                    e = launch(splat_shear_kernel<NT(), NEED_U(), UNIT(), BC(), VPL()>, dim3(sg.total), dim3(NT()), smem,
+                               s, d_I, d_u, go, I, u, dt, nc, sg, umode, addgo);
+            });
+        }, need_u, unit_step, bc);
+    });
     if (e != hipSuccess) return fail_hip(e, "interp_backward (sheared-window splat)");
     note_path(LP_SPLAT_SHEAR);
     return finish_launch(s, "interp_backward (sheared-window splat)");
@@ -1127,25 +1099,16 @@ static bool make_tiles(TileGeom &tg, const Geom &g, const Geom &gs, int64_t nn, 
 
 std::atomic<int> g_splat_mc{1};  // 1: multi-channel single-pass form of interp_backward where it applies
 
-template <typename R, int MODE, bool BC, bool NEED_U, int NT, int VPL, bool MC = false>
-static hipError_t launch_tiled(R *d_I, R *d_u, const R *go, const R *I, const PosArgs &pa, int nc,
-                               const TileGeom &tg, size_t smem, hipStream_t s) {
-    auto k = splat_tiled_kernel<R, MODE, BC, NEED_U, NT, VPL, MC>;
-    if (smem > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(k),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-        if (e != hipSuccess) return e;
-    }
-    hipLaunchKernelGGL(k, dim3(tg.total), dim3(NT), smem, s, d_I, d_u, go, I, pa, nc, tg);
-    return hipSuccess;
-}
-
-template <typename R, int MODE, bool BC, bool NEED_U, int VPL>
-static hipError_t by_threads(R *d_I, R *d_u, const R *go, const R *I, const PosArgs &pa, int nc, const TileGeom &tg,
-                             size_t smem, int nt, hipStream_t s) {
-    if (nt >= 1024) return launch_tiled<R, MODE, BC, NEED_U, 1024, VPL>(d_I, d_u, go, I, pa, nc, tg, smem, s);
-    if (nt >= 512) return launch_tiled<R, MODE, BC, NEED_U, 512, VPL>(d_I, d_u, go, I, pa, nc, tg, smem, s);
-    return launch_tiled<R, MODE, BC, NEED_U, 256, VPL>(d_I, d_u, go, I, pa, nc, tg, smem, s);
+// nt: 256, 512 or 1024 (make_tiles)
+template <typename R, int MODE, bool BC, bool NEED_U, int VPL, bool MC = false>
+static hipError_t launch_tiled(R *d_I, R *d_u, const R *go, const R *I, const PosArgs &pa, int nc, const TileGeom &tg,
+                               size_t smem, int nt, hipStream_t s) {
+    hipError_t e = hipErrorInvalidValue;
+    with_int<256, 512, 1024>(nt, [&](auto NT) {
+        e = launch(splat_tiled_kernel<R, MODE, BC, NEED_U, NT(), VPL, MC>, dim3(tg.total), dim3(NT()), smem, s, d_I, d_u,
+                   go, I, pa, nc, tg);
+    });
+    return e;
 }
 
 // Returns LAGO_OK / error, or 1 when this shape is left to the plain kernel.
@@ -1172,7 +1135,6 @@ int interp_backward_lds(R *d_I, R *d_u, const R *go, const R *I, const R *u, dou
     pa.dt = dt;
     pa.umode = umode;
     pa.addgo = addgo;
-    hipError_t e;
     const bool unit = unit_dt<R>(dt);
     // several channels with d_u wanted: the single-pass multi-channel form when one workgroup pass
     // covers the tile (1024 threads x 4 voxels for the default 4096-voxel tile)
@@ -1181,30 +1143,18 @@ int interp_backward_lds(R *d_I, R *d_u, const R *go, const R *I, const R *u, dou
     if constexpr (sizeof(R) == 4)
     if (g_splat_mc && vec && need_u && nc > 1 && tg.tile_groups <= 1024u * V) {
         const int ntm = tg.tile_groups <= 256u * V ? 256 : (tg.tile_groups <= 512u * V ? 512 : 1024);
-#define GOMC(M, B)                                                                                                 \
-    e = ntm == 1024  ? launch_tiled<R, M, B, true, 1024, V, true>(d_I, d_u, go, I, pa, nc, tg, smem, s)           \
-        : ntm == 512 ? launch_tiled<R, M, B, true, 512, V, true>(d_I, d_u, go, I, pa, nc, tg, smem, s)            \
-                     : launch_tiled<R, M, B, true, 256, V, true>(d_I, d_u, go, I, pa, nc, tg, smem, s)
-        if (unit) {
-            if (bc) GOMC(POS_DISP_UNIT, true); else GOMC(POS_DISP_UNIT, false);
-        } else {
-            if (bc) GOMC(POS_DISP, true); else GOMC(POS_DISP, false);
-        }
-#undef GOMC
+        const hipError_t e = with_flags([&](auto UNIT, auto BC) {
+            constexpr int MODE = UNIT() ? POS_DISP_UNIT : POS_DISP;
+            return launch_tiled<R, MODE, BC(), true, V, true>(d_I, d_u, go, I, pa, nc, tg, smem, ntm, s);
+        }, unit, bc);
         if (e != hipSuccess) return fail_hip(e, "interp_backward (tiled splat)");
         note_path(LP_SPLAT_TILED);
         return finish_launch(s, "interp_backward (tiled splat)");
     }
-#define GO(B, U) \
-    e = !vec   ? by_threads<R, POS_DISP, B, U, 1>(d_I, d_u, go, I, pa, nc, tg, smem, nt, s)          \
-        : unit ? by_threads<R, POS_DISP_UNIT, B, U, V>(d_I, d_u, go, I, pa, nc, tg, smem, nt, s)     \
-               : by_threads<R, POS_DISP, B, U, V>(d_I, d_u, go, I, pa, nc, tg, smem, nt, s)
-    if (bc) {
-        if (need_u) GO(true, true); else GO(true, false);
-    } else {
-        if (need_u) GO(false, true); else GO(false, false);
-    }
-#undef GO
+    const hipError_t e = with_flags([&](auto BC, auto NEED_U, auto VEC, auto UNIT) {
+        constexpr int MODE = VEC() && UNIT() ? POS_DISP_UNIT : POS_DISP, VPL = VEC() ? V : 1;
+        return launch_tiled<R, MODE, BC(), NEED_U(), VPL>(d_I, d_u, go, I, pa, nc, tg, smem, nt, s);
+    }, bc, need_u, vec, unit);
     if (e != hipSuccess) return fail_hip(e, "interp_backward (tiled splat)");
     note_path(LP_SPLAT_TILED);
     return finish_launch(s, "interp_backward (tiled splat)");
@@ -1227,8 +1177,8 @@ int affine_splat_lds(R *d_I, const R *go, const R *A, const R *T, int nc, int64_
     pa.A = A;
     pa.T = T;
     pa.gate = gate;
-    hipError_t e = bc ? by_threads<R, POS_AFFINE, true, false, 4>(d_I, nullptr, go, nullptr, pa, nc, tg, smem, nt, s)
-                      : by_threads<R, POS_AFFINE, false, false, 4>(d_I, nullptr, go, nullptr, pa, nc, tg, smem, nt, s);
+    hipError_t e = bc ? launch_tiled<R, POS_AFFINE, true, false, 4>(d_I, nullptr, go, nullptr, pa, nc, tg, smem, nt, s)
+                      : launch_tiled<R, POS_AFFINE, false, false, 4>(d_I, nullptr, go, nullptr, pa, nc, tg, smem, nt, s);
     if (e != hipSuccess) return fail_hip(e, "affine_interp_backward (tiled splat)");
     return finish_launch(s, "affine_interp_backward (tiled splat)");
 }
@@ -1249,7 +1199,7 @@ int regrid_splat_lds(R *d_I, const R *go, int64_t nplanes, const Geom &g, const 
         pa.O[d] = O[d];
         pa.S[d] = S[d];
     }
-    hipError_t e = by_threads<R, POS_REGRID, false, false, 4>(d_I, nullptr, go, nullptr, pa, 1, tg, smem, nt, s);
+    hipError_t e = launch_tiled<R, POS_REGRID, false, false, 4>(d_I, nullptr, go, nullptr, pa, 1, tg, smem, nt, s);
     if (e != hipSuccess) return fail_hip(e, "regrid_backward (tiled splat)");
     return finish_launch(s, "regrid_backward (tiled splat)");
 }
