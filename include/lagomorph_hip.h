@@ -296,7 +296,42 @@ long long lago_reversed_launches(void);
      * taps are multiplied too); the all-zero-radii copy is exact.  No counterpart in the reference. */                                                                             \
     int lago_gauss_smooth##SUF(REAL *out, const REAL *in, REAL *scratch, const int *radii, const double *taps,      \
                                int mode, double alpha, int accumulate, int dim, int64_t rows, int64_t nx,           \
-                               int64_t ny, int64_t nz, void *stream);
+                               int64_t ny, int64_t nz, void *stream);                                               \
+    /* lncc (no counterpart in the reference): Gaussian-windowed local normalised cross-correlation of two fields   \
+     * I, J of `rows` = N*C scalar fields of extent (nx, ny[, nz]), in four stages that the caller chains.  With G  \
+     * the operator of lago_gauss_smooth (same radii, taps and border modes):                                       \
+     *       A = G I, B = G J, C = G(I I), D = G(I J), E = G(J J)                                                   \
+     *       sI = C - A^2, sJ = E - B^2, sX = D - A B, cc = sX^2 / (sI sJ + eps)             (nothing is clamped)   \
+     * lago_lncc_moments: out (5, rows, *sp) = (A, B, C, D, E).  One kernel along the last axis always runs (at     \
+     * radius 0 it only forms the products): it reads I and J once, forms the products in double (exact for float)  \
+     * and writes the five rows; the other axes with r > 0 then run the pass kernels of lago_gauss_smooth over the  \
+     * 5 rows stacked fields, first axis first.  Every stored intermediate is rounded to REAL.  radii / taps: as for\
+     * lago_gauss_smooth, HOST arrays read during the call and passed to the kernels by value (the call may be      \
+     * captured in a graph).  scratch: one tensor like out, needed when an axis besides the last has r > 0 (else may\
+     * be NULL), clobbered.  out and scratch may not overlap I, J or each other; I may equal J.  No atomics: the    \
+     * same bits from call to call.  No counterpart in the reference. */                                            \
+    int lago_lncc_moments##SUF(REAL *out, const REAL *I, const REAL *J, REAL *scratch, const int *radii,            \
+                               const double *taps, int mode, int dim, int64_t rows, int64_t nx, int64_t ny,         \
+                               int64_t nz, void *stream);                                                           \
+    /* lago_lncc_cc: cc (n) from the moments (5, n), n = rows * voxels; pointwise, arithmetic in double for both    \
+     * precisions, rounded once.  eps >= 0.  cc may not overlap the moments.  No counterpart in the reference. */   \
+    int lago_lncc_cc##SUF(REAL *cc, const REAL *moments, double eps, int64_t n, void *stream);                      \
+    /* lago_lncc_coeffs: the fields under the G's of the backward for an upstream gradient g (n) on cc.  With       \
+     * den = sI sJ + eps, cX = 2 sX / den, cI = -sX^2 sJ / den^2, cJ = -sX^2 sI / den^2:                            \
+     *       dI = G[g (-2 A cI - B cX)] + 2 I G[g cI] + J G[g cX]                                                   \
+     *       dJ = G[g (-2 B cJ - A cX)] + 2 J G[g cJ] + I G[g cX]                                                   \
+     * which = 1: coef (3, n) = (g (-2 A cI - B cX), g cI, g cX); which = 2: (g (-2 B cJ - A cX), g cJ, g cX);      \
+     * which = 3: (5, n) = the three of dI, then g (-2 B cJ - A cX), g cJ.  The layout is that of `k rows` stacked  \
+     * fields: ONE lago_gauss_smooth call with rows = k * rows filters them.  Pointwise, in double, rounded once;   \
+     * coef may not overlap an input.  No counterpart in the reference. */                                          \
+    int lago_lncc_coeffs##SUF(REAL *coef, const REAL *moments, const REAL *g, double eps, int which, int64_t n,     \
+                              void *stream);                                                                        \
+    /* lago_lncc_combine: dI and / or dJ (n each; the one `which` does not name may be NULL) from `smoothed`, the   \
+     * filtered output of lago_lncc_coeffs with the same `which`, and I, J: S0 + 2 I S1 + J S2 (and the same with   \
+     * J's fields and the shared G[g cX]).  Pointwise, in double, rounded once; an output may not overlap an input  \
+     * or the other output.  No counterpart in the reference. */                                                    \
+    int lago_lncc_combine##SUF(REAL *dI, REAL *dJ, const REAL *smoothed, const REAL *I, const REAL *J, int which,   \
+                               int64_t n, void *stream);
 
 LAGO_DECLARE(float, _f32)
 LAGO_DECLARE(double, _f64)

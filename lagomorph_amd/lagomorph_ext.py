@@ -74,6 +74,10 @@ _SIGS = {
     "lago_invert_disp_forward": [_vp, _vp, _int, _int, _i64, _i64, _i64, _i64, _vp],
     "lago_invert_disp_adjoint": [_vp, _vp, _vp, _vp, _int, _i64, _i64, _i64, _i64, _vp],
     "lago_gauss_smooth": [_vp, _vp, _vp, _vp, _vp, _int, _dbl, _int, _int, _i64, _i64, _i64, _i64, _vp],
+    "lago_lncc_moments": [_vp, _vp, _vp, _vp, _vp, _vp, _int, _int, _i64, _i64, _i64, _i64, _vp],
+    "lago_lncc_cc": [_vp, _vp, _dbl, _i64, _vp],
+    "lago_lncc_coeffs": [_vp, _vp, _vp, _dbl, _int, _i64, _vp],
+    "lago_lncc_combine": [_vp, _vp, _vp, _vp, _vp, _int, _i64, _vp],
     "lago_fluid_metric": [_vp, _vp, _vp, _i64, _int, _vp, _vp, _vp, _vp, _vp, _vp, _dbl, _dbl, _dbl, _int, _i64, _i64,
                           _i64, _i64, _vp],
     "lago_fluid_metric_scaled": [_vp, _vp, _vp, _i64, _int, _vp, _vp, _vp, _vp, _vp, _vp, _dbl, _dbl, _dbl, _int, _i64,
@@ -584,6 +588,111 @@ def gaussian_smooth_forward(x, radii, taps, mode, alpha=1.0, out=None, accumulat
     _call("lago_gauss_smooth", x, _ptr(out), _ptr(x), _ptr(scratch), rad, half, GAUSS_MODES[mode], float(alpha),
           int(bool(accumulate)), dim, x.size(0) * x.size(1), nx, ny, nz)
     return out
+
+
+def _gauss_half_taps(what, dim, radii, taps, mode):
+    """The radius / tap checks of gaussian_smooth_forward: (radii as ints, the half-tap block lago_gauss_smooth takes)."""
+    if mode not in GAUSS_MODES:
+        raise ValueError(f"{what}: unknown mode {mode!r} (one of {sorted(GAUSS_MODES)})")
+    radii = [int(r) for r in radii]
+    if len(radii) != dim or len(taps) != dim:
+        raise ValueError(f"{what}: {dim} radii and tap vectors are needed, one per spatial axis")
+    half = (ctypes.c_double * (dim * (GAUSS_MAX_RADIUS + 1)))()
+    for a, r in enumerate(radii):
+        if r < 0 or r > GAUSS_MAX_RADIUS:
+            raise ValueError(f"{what}: radius {r} on axis {a} is outside 0..{GAUSS_MAX_RADIUS}")
+        if r > 0:
+            t = [float(v) for v in taps[a]]
+            if len(t) != 2 * r + 1:
+                raise ValueError(f"{what}: axis {a} needs {2 * r + 1} taps, got {len(t)}")
+            if any(t[r + k] != t[r - k] for k in range(1, r + 1)):
+                raise ValueError(f"{what}: the taps must be symmetric")
+            for k in range(r + 1):
+                half[a * (GAUSS_MAX_RADIUS + 1) + k] = t[r + k]
+    return radii, half
+
+
+def _check_lncc_pair(I, J):
+    for x, nm in ((I, "I"), (J, "J")):
+        if not isinstance(x, torch.Tensor):
+            raise TypeError(f"{nm} must be a torch.Tensor")
+    _suffix(I)
+    dim, nx, ny, nz = _spatial(I)
+    if dim not in (2, 3):
+        raise RuntimeError("Only two- and three-dimensional lncc is supported")
+    if J.shape != I.shape:
+        raise RuntimeError(f"lncc: I {tuple(I.shape)} and J {tuple(J.shape)} must have the same shape")
+    _same(I, J)
+    return dim, nx, ny, nz
+
+
+def _check_lncc_eps(eps):
+    eps = float(eps)
+    if not eps >= 0.0:
+        raise ValueError(f"lncc: eps must not be negative (got {eps})")
+    return eps
+
+
+def lncc_moments(I, J, radii, taps, mode):
+    """The five windowed moments (G I, G J, G(I I), G(I J), G(J J)) of I, J (N, C, *sp) as one (5, N, C, *sp) tensor
+    (csrc/lncc.hip: lncc_moments_kernel along the last axis, then the pass kernels of gaussian_smooth over the stacked
+    rows).  radii, taps, mode: as for gaussian_smooth_forward.  One scratch tensor like the result is allocated here
+    when an axis besides the last is filtered.  Not in the reference; no CPU path."""
+    dim, nx, ny, nz = _check_lncc_pair(I, J)
+    radii, half = _gauss_half_taps("lncc", dim, radii, taps, mode)
+    if not I.is_cuda:
+        raise RuntimeError("I must be a CUDA tensor")
+    I, J = I.contiguous(), J.contiguous()
+    out = torch.empty((5,) + tuple(I.shape), dtype=I.dtype, device=I.device)
+    scratch = torch.empty_like(out) if any(r > 0 for r in radii[:-1]) else None
+    rad = (ctypes.c_int * dim)(*radii)
+    _call("lago_lncc_moments", I, _ptr(out), _ptr(I), _ptr(J), _ptr(scratch), rad, half, GAUSS_MODES[mode], dim,
+          I.size(0) * I.size(1), nx, ny, nz)
+    return out
+
+
+def lncc_cc(moments, eps):
+    """cc = sX^2 / (sI sJ + eps) (N, C, *sp) from the moments of lncc_moments (csrc/lncc.hip: lncc_cc_kernel)."""
+    if not isinstance(moments, torch.Tensor):
+        raise TypeError("moments must be a torch.Tensor")
+    _suffix(moments)
+    if moments.dim() not in (5, 6) or moments.size(0) != 5:
+        raise RuntimeError(f"lncc_cc: moments must be (5, N, C, *spatial), got {tuple(moments.shape)}")
+    eps = _check_lncc_eps(eps)
+    _check_input(moments, "moments")
+    cc = torch.empty(tuple(moments.shape[1:]), dtype=moments.dtype, device=moments.device)
+    _call("lago_lncc_cc", moments, _ptr(cc), _ptr(moments), eps, cc.numel())
+    return cc
+
+
+def lncc_backward(grad_out, I, J, moments, radii, taps, mode, eps, need_I=True, need_J=True):
+    """(dI, dJ) of cc = lncc for the upstream gradient grad_out, from the saved moments: the coefficient fields
+    (lncc_coeff_kernel), ONE stacked gaussian_smooth_forward over them, and lncc_combine_kernel (csrc/lncc.hip).  A
+    gradient that is not needed is None.  Not in the reference; no CPU path."""
+    dim, nx, ny, nz = _check_lncc_pair(I, J)
+    radii, _ = _gauss_half_taps("lncc", dim, radii, taps, mode)
+    eps = _check_lncc_eps(eps)
+    if not isinstance(grad_out, torch.Tensor) or not isinstance(moments, torch.Tensor):
+        raise TypeError("grad_out and moments must be torch.Tensors")
+    if grad_out.shape != I.shape or tuple(moments.shape) != (5,) + tuple(I.shape):
+        raise RuntimeError("lncc_backward: grad_out must have the shape of I and moments be (5, *I.shape)")
+    _same(I, grad_out, moments)
+    if not (need_I or need_J):
+        return None, None
+    if not I.is_cuda:
+        raise RuntimeError("I must be a CUDA tensor")
+    I, J, grad_out, moments = I.contiguous(), J.contiguous(), grad_out.contiguous(), moments.contiguous()
+    which = (1 if need_I else 0) | (2 if need_J else 0)
+    k = 5 if which == 3 else 3
+    n = I.numel()
+    coef = torch.empty((k * I.size(0), I.size(1)) + tuple(I.shape[2:]), dtype=I.dtype, device=I.device)
+    _call("lago_lncc_coeffs", I, _ptr(coef), _ptr(moments), _ptr(grad_out), eps, which, n)
+    sm = gaussian_smooth_forward(coef, radii, taps, mode)
+    del coef
+    d_I = torch.empty_like(I) if need_I else None
+    d_J = torch.empty_like(J) if need_J else None
+    _call("lago_lncc_combine", I, _ptr(d_I), _ptr(d_J), _ptr(sm), _ptr(I), _ptr(J), which, n)
+    return d_I, d_J
 
 
 def fluid_operator(Fmv, inverse, cosluts, sinluts, alpha, beta, gamma):

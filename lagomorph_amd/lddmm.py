@@ -273,7 +273,7 @@ def _fused_step_ok(I, m, img, metric, integration_steps):
 
 
 def _lddmm_step_fused(I, m, img, metric, dataset_size, integration_steps, reg_weight, learning_rate_pose,
-                      momentum_preconditioning, whole=None, after_image_backward=None):
+                      momentum_preconditioning, whole=None, after_image_backward=None, similarity=None):
     """`lddmm_step` with the momentum side written out by hand: the shoot and its reverse sweep (`_shoot`,
     `_shoot_reverse`), the regulariser <sharp(m), m> and its gradient, and the descent step, with every elementwise
     sum in one pass (`lagomorph_ext.lincomb`).  Autograd is kept for the image side -- interp of the atlas, the
@@ -281,7 +281,8 @@ def _lddmm_step_fused(I, m, img, metric, dataset_size, integration_steps, reg_we
     as in the plain form.  Same formulas; sums in a different order (rounding only).
     `whole` = (numel, items) of the WHOLE minibatch when (m, img) is a sub-batch of it (`_lddmm_step_split`): the
     normalisers of the loss are the minibatch's (lddmm.py:308-313), so the parts' losses and gradients simply add.
-    `after_image_backward`: called once I.grad holds this call's splat (the split records a stream event there)."""
+    `after_image_backward`: called once I.grad holds this call's splat (the split records a stream event there).
+    `similarity`: see `lddmm_step`."""
     numel, items = (img.numel(), img.shape[0]) if whole is None else whole
     regrid_momenta = tuple(m.shape[2:]) != tuple(I.shape[2:])
     dt = 1.0 / integration_steps
@@ -291,7 +292,10 @@ def _lddmm_step_fused(I, m, img, metric, dataset_size, integration_steps, reg_we
         h, steps, _ = _shoot(metric, m, None, dt, integration_steps, v, True)
     h.requires_grad_(True)
     hh = regrid(h, shape=I.shape[2:]) if regrid_momenta else h
-    img_term = torch.nn.functional.mse_loss(deform.interp(I, hh), img, reduction="sum") / numel
+    if similarity is None:
+        img_term = torch.nn.functional.mse_loss(deform.interp(I, hh), img, reduction="sum") / numel
+    else:
+        img_term = similarity(deform.interp(I, hh), img) / numel
     img_term.backward()
     if after_image_backward is not None:
         after_image_backward()
@@ -334,7 +338,7 @@ LDDMM_STEP_STREAMS = 1
 
 
 def _lddmm_step_split(I, m, img, metric, dataset_size, integration_steps, reg_weight, learning_rate_pose,
-                      momentum_preconditioning):
+                      momentum_preconditioning, similarity=None):
     """`_lddmm_step_fused` over sub-batches on side streams; None when the split does not apply."""
     parts = LDDMM_STEP_STREAMS
     B = m.size(0)
@@ -355,7 +359,7 @@ def _lddmm_step_split(I, m, img, metric, dataset_size, integration_steps, reg_we
             ev = torch.cuda.Event()
             res.append(_lddmm_step_fused(Ik, m[sl], img[sl], metric, dataset_size, integration_steps, reg_weight,
                                          learning_rate_pose, momentum_preconditioning, whole=whole,
-                                         after_image_backward=ev.record))
+                                         after_image_backward=ev.record, similarity=similarity))
             leaves.append(Ik)
             events.append(ev)
     if want_I:
@@ -382,20 +386,22 @@ def _lddmm_step_split(I, m, img, metric, dataset_size, integration_steps, reg_we
 
 
 def lddmm_step(I, m, img, metric, dataset_size, integration_steps=5, reg_weight=1e2, learning_rate_pose=2e2,
-               momentum_preconditioning=False):
+               momentum_preconditioning=False, similarity=None):
     """One matching step of the atlas builder for a minibatch (lddmm.py:300-325).
 
     I: atlas image (1, 1, *sp) with requires_grad as the caller wishes (its .grad accumulates),
     m: momenta (B, d, *msp) -- updated in place by gradient descent, img: (B, 1, *sp).
     Returns (m, loss, reg_term) with loss/reg already scaled by B / dataset_size, all on device
-    (no host synchronisation)."""
+    (no host synchronisation).
+    similarity (not in the reference): None for the squared difference, or a callable (Idef, img) -> a 0-dim tensor
+    summed over the minibatch, e.g. `LNCCSimilarity(sigma)`; the image term is then similarity(Idef, img) / numel."""
     if _fused_step_ok(I, m, img, metric, integration_steps):
         out = _lddmm_step_split(I, m, img, metric, dataset_size, integration_steps, reg_weight, learning_rate_pose,
-                                momentum_preconditioning)
+                                momentum_preconditioning, similarity)
         if out is not None:
             return out
         return _lddmm_step_fused(I, m, img, metric, dataset_size, integration_steps, reg_weight, learning_rate_pose,
-                                 momentum_preconditioning)
+                                 momentum_preconditioning, similarity=similarity)
     m.requires_grad_(True)
     if m.grad is not None:
         m.grad.detach_()
@@ -409,7 +415,10 @@ def lddmm_step(I, m, img, metric, dataset_size, integration_steps=5, reg_weight=
     reg_term = reg_weight * (v * m).sum() / img.numel()
     if regrid_momenta:  # account for downscaling in averaging (lddmm.py:311-312)
         reg_term = reg_term * (I.numel() / v[0, 0, ...].numel())
-    loss = torch.nn.functional.mse_loss(Idef, img, reduction="sum") / img.numel() + reg_term
+    if similarity is None:
+        loss = torch.nn.functional.mse_loss(Idef, img, reduction="sum") / img.numel() + reg_term
+    else:
+        loss = similarity(Idef, img) / img.numel() + reg_term
     loss.backward()
     with torch.no_grad():
         norm_factor = img.shape[0] / dataset_size
@@ -478,7 +487,8 @@ class LDDMMAtlasBuilder:
     def __init__(self, images, batch_size=8, lddmm_steps=1, lddmm_integration_steps=5, image_update_freq=0,
                  reg_weight=1e2, learning_rate_pose=2e2, learning_rate_image=1e4, metric=None, momentum_shape=None,
                  image_shape=None, momentum_preconditioning=False, I0=None, ms=None, world_size=1, rank=0,
-                 dataset_size=None, checkpoint_format=None, overlap_allreduce=True, force_collectives=False):
+                 dataset_size=None, checkpoint_format=None, overlap_allreduce=True, force_collectives=False,
+                 similarity=None):
         self.images = images  # this rank's shard: (n_local, 1, *sp) on the device
         self.batch_size = batch_size
         self.lddmm_steps = lddmm_steps
@@ -489,6 +499,7 @@ class LDDMMAtlasBuilder:
         self.learning_rate_image = learning_rate_image
         self.metric = metric if metric is not None else FluidMetric([0.1, 0, 0.01])  # lddmm.py:213
         self.momentum_preconditioning = momentum_preconditioning
+        self.similarity = similarity   # the image term of lddmm_step (None: the squared difference)
         self.world_size = world_size
         self.rank = rank
         self.checkpoint_format = checkpoint_format
@@ -596,7 +607,8 @@ class LDDMMAtlasBuilder:
             m, loss, reg = lddmm_step(self.I, m, img, self.metric, self.dataset_size,
                                       integration_steps=self.lddmm_integration_steps, reg_weight=self.reg_weight,
                                       learning_rate_pose=self.learning_rate_pose,
-                                      momentum_preconditioning=self.momentum_preconditioning)
+                                      momentum_preconditioning=self.momentum_preconditioning,
+                                      similarity=self.similarity)
         self._reduce_now = False
         self.ms[b] = m
         self.image_iters += 1
