@@ -191,6 +191,47 @@ __device__ __forceinline__ Vox locate(const Geom &g) {
     return v;
 }
 
+// The walk of the slab-unrolled 3D kernels (grid: slab_grid): a workgroup covers U slabs of kBlock consecutive voxels
+// of batch item n, lane t owns voxel t of every slab.  Past-the-end lanes (ok[e] false) are redirected to voxel 0 for
+// their loads; what coordinates they get is the caller's business.
+template <int U>
+struct Slabs {
+    uint32_t n;
+    uint32_t s[U];
+    bool ok[U];
+    __device__ __forceinline__ Slabs(const Geom &g, uint32_t nbx_u, uint32_t nblocks_u) {
+        const uint32_t Lb = block_order(blockIdx.x, nblocks_u, g.rev);
+        n = Lb / nbx_u;  // uniform: scalar division
+        const uint32_t bx = Lb - n * nbx_u;
+#pragma unroll
+        for (int e = 0; e < U; ++e) {
+            s[e] = (bx * U + e) * kBlock + threadIdx.x;
+            ok[e] = s[e] < g.nvox;
+            if (!ok[e]) s[e] = 0;
+        }
+    }
+    // f(e, i, j, k) for every slab: one fast division for e = 0, then +256 voxels per slab as (+qj rows, +rk voxels)
+    // with at most one carry each (host guarantees qj + 1 < ny)
+    template <typename F>
+    __device__ __forceinline__ void walk(const Geom &g, F &&f) const {
+        uint32_t ci = g.dyz.div(s[0]);
+        const uint32_t r = s[0] - ci * (uint32_t)(g.ny * g.nz);
+        uint32_t cj = g.dz.div(r);
+        uint32_t ck = r - cj * (uint32_t)g.nz;
+        const uint32_t qj = (uint32_t)kBlock / (uint32_t)g.nz, rk = (uint32_t)kBlock % (uint32_t)g.nz;  // uniform
+#pragma unroll
+        for (int e = 0; e < U; ++e) {
+            if (e > 0) {
+                ck += rk;
+                cj += qj;
+                if (ck >= (uint32_t)g.nz) { ck -= g.nz; ++cj; }
+                if (cj >= (uint32_t)g.ny) { cj -= g.ny; ++ci; }
+            }
+            f(e, (int)ci, (int)cj, (int)ck);
+        }
+    }
+};
+
 // ---- arithmetic contract ----------------------------------------------------
 // Every `a*b + c` of the reference is evaluated as one fused multiply-add and a
 // sum of two products `a*b + c*d` as fma(a, b, c*d) (left product fused): the
@@ -327,6 +368,20 @@ __device__ __forceinline__ void buf_load2<double>(BufRsrc r, uint32_t off, doubl
     hi = __builtin_bit_cast(double, q.b);
 }
 
+// The trilinear value (include/interp.h:115-122) from the four (zb, zb + 1) pairs of rows (fx,fy) (cx,fy) (cx,cy) (fx,cy),
+// for Lerp3::value and GWLerp::value.  The z-border selection is made AFTER the two (x, y) interpolations: the floor-z
+// group c0..c3 is either the four `lo` halves or the four `hi` halves (f_hi is one flag for all four rows), the ceil-z
+// group likewise, and both groups go through the same expression G -- so fma(omv, f_hi ? G(hi) : G(lo), v * (c_lo ? G(lo)
+// : G(hi))) is value_of(c) bit for bit with two selects instead of eight (the gather kernels are half bound by vector
+// instruction issue: 48 of Ad_star's 424 vector instructions per thread were these selects).
+template <typename R>
+__device__ __forceinline__ R lerp3_pairs(const R (&lo)[4], const R (&hi)[4], R t, R u, R v, bool f_hi, bool c_lo) {
+    const R omt = (R)1.f - t, omu = (R)1.f - u, omv = (R)1.f - v;
+    const R glo = lg_fma(omu, lg_fma(omt, lo[0], t * lo[1]), u * lg_fma(omt, lo[3], t * lo[2]));
+    const R ghi = lg_fma(omu, lg_fma(omt, hi[0], t * hi[1]), u * lg_fma(omt, hi[3], t * hi[2]));
+    return lg_fma(omv, f_hi ? ghi : glo, v * (c_lo ? glo : ghi));
+}
+
 // Trilinear stencil.  The 8 corners are 4 (x, y) rows times the z pair
 // (floor, floor+1), which is contiguous in memory: each row is fetched with ONE
 // pair load at z = zb = min(clamped floor, nz-2); when the sample lies beyond a z
@@ -386,11 +441,6 @@ struct Lerp3 {
             c[q + 4] = c_lo ? lo : hi;
         }
     }
-    // include/interp.h:115-122.  The z-border selection is made AFTER the two (x, y) interpolations: the floor-z group
-    // c0..c3 is either the four `lo` halves or the four `hi` halves (f_hi is one flag for all four rows), the ceil-z group
-    // likewise, and both groups go through the same expression G -- so fma(omv, f_hi ? G(hi) : G(lo), v * (c_lo ? G(lo) :
-    // G(hi))) is value_of(c) bit for bit with two selects instead of eight (the gather kernels are half bound by vector
-    // instruction issue: 48 of Ad_star's 424 vector instructions per thread were these selects).
     __device__ __forceinline__ R value(const R *__restrict__ img) const {
         if (THIN_OK && thin) {
             R c[8];
@@ -401,10 +451,7 @@ struct Lerp3 {
         R lo[4], hi[4];
 #pragma unroll
         for (int q = 0; q < 4; ++q) buf_load2<R>(r, rb[q], lo[q], hi[q]);
-        const R omt = (R)1.f - t, omu = (R)1.f - u, omv = (R)1.f - v;
-        const R glo = lg_fma(omu, lg_fma(omt, lo[0], t * lo[1]), u * lg_fma(omt, lo[3], t * lo[2]));
-        const R ghi = lg_fma(omu, lg_fma(omt, hi[0], t * hi[1]), u * lg_fma(omt, hi[3], t * hi[2]));
-        return lg_fma(omv, f_hi ? ghi : glo, v * (c_lo ? glo : ghi));
+        return lerp3_pairs(lo, hi, t, u, v, f_hi, c_lo);
     }
     __device__ __forceinline__ R value_of(const R (&c)[8]) const {
         const R omt = (R)1.f - t, omu = (R)1.f - u, omv = (R)1.f - v;

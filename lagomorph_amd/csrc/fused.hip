@@ -51,53 +51,28 @@ __global__ __launch_bounds__(kBlock) void compose_kernel(R *__restrict__ out, co
     }
 }
 
-// Unrolled 3D variant (see interp_fwd3_unroll_kernel in interp.hip): U slabs of 256 consecutive
-// voxels per workgroup, one voxel of each slab per lane.
+// Unrolled 3D variant (Slabs of common.hpp; why slabs: see interp_fwd3_unroll_kernel in interp.hip): U slabs of 256
+// consecutive voxels per workgroup, one voxel of each slab per lane.
 template <typename R, int U, bool UNIT>
 __global__ __launch_bounds__(kBlock) void compose3_unroll_kernel(R *__restrict__ out, const R *__restrict__ u,
                                                                  const R *__restrict__ v, double ds, double dt, Geom g,
                                                                  uint32_t nbx_u, uint32_t nblocks_u) {
-    const uint32_t Lb = block_order(blockIdx.x, nblocks_u, g.rev);
-    const uint32_t n = Lb / nbx_u;
-    const uint32_t bx = Lb - n * nbx_u;
+    const Slabs<U> S(g, nbx_u, nblocks_u);
     const size_t nv = g.nvox;
-    const R *un = u + (size_t)n * 3 * nv;
-    const R *vn = v + (size_t)n * 3 * nv;
-    R *on = out + (size_t)n * 3 * nv;
+    const R *un = u + (size_t)S.n * 3 * nv;
+    const R *vn = v + (size_t)S.n * 3 * nv;
+    R *on = out + (size_t)S.n * 3 * nv;
     const R dsr = (R)ds, dtr = (R)dt;
-    uint32_t s[U];
-    bool ok[U];
     R uu[3][U];
 #pragma unroll
-    for (int e = 0; e < U; ++e) {
-        s[e] = (bx * U + e) * kBlock + threadIdx.x;
-        ok[e] = s[e] < g.nvox;
-        if (!ok[e]) s[e] = 0;
+    for (int e = 0; e < U; ++e)
 #pragma unroll
-        for (int d = 0; d < 3; ++d) uu[d][e] = un[(size_t)d * nv + s[e]];
-    }
+        for (int d = 0; d < 3; ++d) uu[d][e] = un[(size_t)d * nv + S.s[e]];
     Lerp3<R, false> L[U];  // nz >= 2 guaranteed by the host: no per-sample thin branch
-    uint32_t ci = 0, cj = 0, ck = 0;
-    const uint32_t qj = (uint32_t)kBlock / (uint32_t)g.nz, rk = (uint32_t)kBlock % (uint32_t)g.nz;  // uniform
-#pragma unroll
-    for (int e = 0; e < U; ++e) {
-        // (i, j, k) of slab e: one fast division for e = 0, then +256 voxels per slab as
-        // (+qj rows, +rk voxels) with at most one carry each (host guarantees qj + 1 < ny)
-        if (e == 0) {
-            ci = g.dyz.div(s[0]);
-            const uint32_t r = s[0] - ci * (uint32_t)(g.ny * g.nz);
-            cj = g.dz.div(r);
-            ck = r - cj * (uint32_t)g.nz;
-        } else {
-            ck += rk;
-            cj += qj;
-            if (ck >= (uint32_t)g.nz) { ck -= g.nz; ++cj; }
-            if (cj >= (uint32_t)g.ny) { cj -= g.ny; ++ci; }
-        }
-        const uint32_t i = ci, j = cj, k = ck;
-        L[e].setup(sample_pos_t<R, UNIT>((int)i, ds, uu[0][e]), sample_pos_t<R, UNIT>((int)j, ds, uu[1][e]),
-                   sample_pos_t<R, UNIT>((int)k, ds, uu[2][e]), g.nx, g.ny, g.nz);
-    }
+    S.walk(g, [&](int e, int i, int j, int k) {
+        L[e].setup(sample_pos_t<R, UNIT>(i, ds, uu[0][e]), sample_pos_t<R, UNIT>(j, ds, uu[1][e]),
+                   sample_pos_t<R, UNIT>(k, ds, uu[2][e]), g.nx, g.ny, g.nz);
+    });
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
         R o[U];
@@ -109,7 +84,7 @@ __global__ __launch_bounds__(kBlock) void compose3_unroll_kernel(R *__restrict__
         }
 #pragma unroll
         for (int e = 0; e < U; ++e)
-            if (ok[e]) on[(size_t)c * nv + s[e]] = o[e];
+            if (S.ok[e]) on[(size_t)c * nv + S.s[e]] = o[e];
     }
 }
 
@@ -254,26 +229,25 @@ static size_t padded_smem(size_t smem) {
     return smem;
 }
 
-// returns 1 when the shape is left to the other kernels
+// returns kNotTaken when the shape is left to the other kernels
 template <typename R>
 static int compose_window_launch(R *out, const R *u, const R *v, double ds, double dt, const Geom &g, int64_t nn,
                                  hipStream_t s) {
     if constexpr (sizeof(R) == 4) {
         GWGrid w;
-        if (!make_gwgrid(w, g, nn) || ((uintptr_t)v & 15u)) return 1;
+        if (!make_gwgrid(w, g, nn) || ((uintptr_t)v & 15u)) return kNotTaken;
         constexpr int NT = GW::NT, U = 8;
-        const size_t smem = GW::lds_bytes<NT>();
         // (compiling the geometry of 128^3 / 160^3 volumes in, as ad_star3_tile_kernel does, costs this kernel 2-15
         // spilled registers at its 128: not done)
         const hipError_t e = with_flags([&](auto UNIT) {
-            return launch(compose3_window_kernel<NT, U, UNIT()>, dim3(w.total), dim3(NT), padded_smem(smem), s, out, u, v,
-                          ds, dt, g, w);
+            return launch(compose3_window_kernel<NT, U, UNIT()>, dim3(w.total), dim3(NT), padded_smem(GW::lds_bytes<NT>()), s,
+                          out, u, v, ds, dt, g, w);
         }, unit_dt<R>(ds));
         if (e != hipSuccess) return fail_hip(e, "compose");
         note_path(LP_GATHER_WINDOW);
         return LAGO_OK;
     }
-    return 1;
+    return kNotTaken;
 }
 
 template <typename R>
@@ -288,7 +262,7 @@ static int compose_impl(R *out, const R *u, const R *v, double ds, double dt, in
     constexpr int U = 2;
     if (dim == 3 && g_interp_vec && g_gather_window && g.nvox >= 32768u) {
         const int rc = compose_window_launch(out, u, v, ds, dt, g, nn, s);
-        if (rc != 1) return rc != LAGO_OK ? rc : finish_launch(s, "compose");
+        if (rc != kNotTaken) return rc != LAGO_OK ? rc : finish_launch(s, "compose");
     }
     uint32_t nbx_u, nb;
     if (dim == 3 && g_interp_vec && slab_grid(g, nn, U, nbx_u, nb)) {
@@ -314,10 +288,19 @@ static int compose_impl(R *out, const R *u, const R *v, double ds, double dt, in
 // interpolated components are rounded to R exactly where the unfused sequence stores them, and the
 // Jacobian product is the expression of jtv_fwd_kernel (diff.hip), so the result is bit-identical.
 
-// 0.5 (f[+1] - f[-1]) with the neighbour offsets clamped at the borders (include/diff.h:55-76)
-template <typename R>
-__device__ __forceinline__ R cdiff(const R *__restrict__ f, int plus, int minus) {
-    return (R)0.5f * (f[plus] - f[minus]);
+// The tail of the three kernels: row c of D phiinv + I times w.  fp[d] / fm[d] are the neighbours of component c at +1 /
+// -1 along axis d, clamped at the borders (0.5 (f+ - f-): include/diff.h:55-76; where they come from is each kernel's
+// own); the dot product is dotw of diff.hip.
+template <typename R, int DIM>
+__device__ __forceinline__ R jac_row_dot(int c, const R (&fp)[DIM], const R (&fm)[DIM], const R (&w)[DIM]) {
+    R gq[DIM];
+#pragma unroll
+    for (int d = 0; d < DIM; ++d) {
+        gq[d] = (R)0.5f * (fp[d] - fm[d]);
+        if (c == d) gq[d] = gq[d] + (R)1.0;
+    }
+    const R sacc = lg_fma(gq[0], w[0], gq[1] * w[1]);
+    return DIM == 3 ? lg_fma(gq[DIM - 1], w[DIM - 1], sacc) : sacc;
 }
 
 template <typename R, int DIM>
@@ -363,61 +346,37 @@ __global__ __launch_bounds__(kBlock) void ad_star_kernel(R *__restrict__ out, R 
     }
 #pragma unroll
     for (int c = 0; c < DIM; ++c) {
-        R gq[DIM];
+        R fp[DIM], fm[DIM];
 #pragma unroll
         for (int d = 0; d < DIM; ++d) {
-            gq[d] = cdiff(pn + (size_t)c * nv, plus[d], minus[d]);
-            if (c == d) gq[d] = gq[d] + (R)1.0;
+            fp[d] = pn[(size_t)c * nv + plus[d]];
+            fm[d] = pn[(size_t)c * nv + minus[d]];
         }
-        R sacc = lg_fma(gq[0], wv[0], gq[1] * wv[1]);  // dotw of diff.hip
-        if (DIM == 3) sacc = lg_fma(gq[2], wv[2], sacc);
-        on[(size_t)c * nv] = sacc;
+        on[(size_t)c * nv] = jac_row_dot(c, fp, fm, wv);
     }
 }
 
-// Unrolled 3D variant: U slabs of 256 consecutive voxels per workgroup, one voxel of each per lane.
+// Unrolled 3D variant (Slabs of common.hpp): U slabs of 256 consecutive voxels per workgroup, one voxel of each per lane.
 template <typename R, int U>
 __global__ __launch_bounds__(kBlock) void ad_star3_unroll_kernel(R *__restrict__ out, R *__restrict__ mphi,
                                                                  const R *__restrict__ phi, const R *__restrict__ m,
                                                                  Geom g, uint32_t nbx_u, uint32_t nblocks_u) {
-    const uint32_t Lb = block_order(blockIdx.x, nblocks_u, g.rev);
-    const uint32_t n = Lb / nbx_u;  // uniform: scalar division
-    const uint32_t bx = Lb - n * nbx_u;
+    const Slabs<U> S(g, nbx_u, nblocks_u);
     const size_t nv = g.nvox;
-    const R *pn = phi + (size_t)n * 3 * nv;
-    const R *mn = m + (size_t)n * 3 * nv;
-    R *on = out + (size_t)n * 3 * nv;
-    uint32_t s[U];
-    bool ok[U];
+    const R *pn = phi + (size_t)S.n * 3 * nv;
+    const R *mn = m + (size_t)S.n * 3 * nv;
+    R *on = out + (size_t)S.n * 3 * nv;
     R pv[3][U];
 #pragma unroll
-    for (int e = 0; e < U; ++e) {
-        s[e] = (bx * U + e) * kBlock + threadIdx.x;
-        ok[e] = s[e] < g.nvox;
-        if (!ok[e]) s[e] = 0;
+    for (int e = 0; e < U; ++e)
 #pragma unroll
-        for (int d = 0; d < 3; ++d) pv[d][e] = pn[(size_t)d * nv + s[e]];
-    }
+        for (int d = 0; d < 3; ++d) pv[d][e] = pn[(size_t)d * nv + S.s[e]];
     Lerp3<R, false> L[U];  // nz >= 2 guaranteed by the host
     int plus[3][U], minus[3][U];
-    uint32_t ci = 0, cj = 0, ck = 0;
-    const uint32_t qj = (uint32_t)kBlock / (uint32_t)g.nz, rk = (uint32_t)kBlock % (uint32_t)g.nz;  // uniform
     const int syz = g.ny * g.nz;
-#pragma unroll
-    for (int e = 0; e < U; ++e) {
-        if (e == 0) {
-            ci = g.dyz.div(s[0]);
-            const uint32_t r = s[0] - ci * (uint32_t)(g.ny * g.nz);
-            cj = g.dz.div(r);
-            ck = r - cj * (uint32_t)g.nz;
-        } else {
-            ck += rk;
-            cj += qj;
-            if (ck >= (uint32_t)g.nz) { ck -= g.nz; ++cj; }
-            if (cj >= (uint32_t)g.ny) { cj -= g.ny; ++ci; }
-        }
+    S.walk(g, [&](int e, int ci, int cj, int ck) {
         // past-the-end lanes were redirected to voxel 0 for their loads; give them its coordinates
-        const int i = ok[e] ? (int)ci : 0, j = ok[e] ? (int)cj : 0, k = ok[e] ? (int)ck : 0;
+        const int i = S.ok[e] ? ci : 0, j = S.ok[e] ? cj : 0, k = S.ok[e] ? ck : 0;
         L[e].setup(sample_pos_t<R, true>(i, 1.0, pv[0][e]), sample_pos_t<R, true>(j, 1.0, pv[1][e]),
                    sample_pos_t<R, true>(k, 1.0, pv[2][e]), g.nx, g.ny, g.nz);
         plus[0][e] = i + 1 < g.nx ? syz : 0;
@@ -426,21 +385,21 @@ __global__ __launch_bounds__(kBlock) void ad_star3_unroll_kernel(R *__restrict__
         minus[1][e] = j > 0 ? -g.nz : 0;
         plus[2][e] = k + 1 < g.nz ? 1 : 0;
         minus[2][e] = k > 0 ? -1 : 0;
-    }
-    R wv[3][U];
+    });
+    R wv[U][3];
 #pragma unroll
     for (int d = 0; d < 3; ++d) {
         if (d) __builtin_amdgcn_sched_barrier(0);  // 16 pair loads in flight at a time, as in interp / compose
 #pragma unroll
-        for (int e = 0; e < U; ++e) wv[d][e] = L[e].value(mn + (size_t)d * nv);
+        for (int e = 0; e < U; ++e) wv[e][d] = L[e].value(mn + (size_t)d * nv);
     }
     if (mphi) {  // the resampled momentum, kept for the backward pass (what interp_forward would have stored)
-        R *mo = mphi + (size_t)n * 3 * nv;
+        R *mo = mphi + (size_t)S.n * 3 * nv;
 #pragma unroll
         for (int d = 0; d < 3; ++d)
 #pragma unroll
             for (int e = 0; e < U; ++e)
-                if (ok[e]) mo[(size_t)d * nv + s[e]] = wv[d][e];
+                if (S.ok[e]) mo[(size_t)d * nv + S.s[e]] = wv[e][d];
     }
     // keep the gather phase and the three stencil phases apart: hoisting the 72 stencil loads above
     // the lerps doubled the register count (201 VGPRs, 2 waves/SIMD) for no gain in overlap
@@ -451,30 +410,23 @@ __global__ __launch_bounds__(kBlock) void ad_star3_unroll_kernel(R *__restrict__
         // neighbours through a buffer descriptor on the component plane: 32-bit byte offsets,
         // no 64-bit address pair per load
         const BufRsrc pc = make_rsrc(pn + (size_t)c * nv, (uint32_t)(nv * sizeof(R)));
-        R fp[3][U], fm[3][U];
+        R fp[U][3], fm[U][3];
 #pragma unroll
         for (int e = 0; e < U; ++e) {
-            const uint32_t sb = s[e] * (uint32_t)sizeof(R);
+            const uint32_t sb = S.s[e] * (uint32_t)sizeof(R);
 #pragma unroll
             for (int d = 0; d < 3; ++d) {
-                fp[d][e] = buf_load1<R>(pc, sb + (uint32_t)(plus[d][e] * (int)sizeof(R)));
-                fm[d][e] = buf_load1<R>(pc, sb + (uint32_t)(minus[d][e] * (int)sizeof(R)));
+                fp[e][d] = buf_load1<R>(pc, sb + (uint32_t)(plus[d][e] * (int)sizeof(R)));
+                fm[e][d] = buf_load1<R>(pc, sb + (uint32_t)(minus[d][e] * (int)sizeof(R)));
             }
         }
 #pragma unroll
         for (int e = 0; e < U; ++e) {
-            R gq[3];
-#pragma unroll
-            for (int d = 0; d < 3; ++d) {
-                gq[d] = (R)0.5f * (fp[d][e] - fm[d][e]);
-                if (c == d) gq[d] = gq[d] + (R)1.0;
-            }
-            const R sacc = lg_fma(gq[2], wv[2][e], lg_fma(gq[0], wv[0][e], gq[1] * wv[1][e]));
-            if (ok[e]) on[(size_t)c * nv + s[e]] = sacc;
+            const R sacc = jac_row_dot(c, fp[e], fm[e], wv[e]);
+            if (S.ok[e]) on[(size_t)c * nv + S.s[e]] = sacc;
         }
     }
 }
-
 
 // Row-tile variant (stencil_tile.hpp): the three phiinv planes of a TX x TY-row tile are staged in LDS with a
 // one-voxel halo and the 18 stencil neighbours of a voxel come from there -- 24 gathered + 3 centre + 3 (2 TX + 2 TY)
@@ -532,12 +484,12 @@ __global__ __launch_bounds__(NT) void ad_star3_tile_kernel(R *__restrict__ out, 
     for (int e = 0; e < U; ++e)
         L[e].setup(sample_pos_t<R, true>(q[e].i, 1.0, pv[0][e]), sample_pos_t<R, true>(q[e].j, 1.0, pv[1][e]),
                    sample_pos_t<R, true>(q[e].k, 1.0, pv[2][e]), g.nx, g.ny, g.nz);
-    R wv[3][U];
+    R wv[U][3];
 #pragma unroll
     for (int d = 0; d < 3; ++d) {
         if (d) __builtin_amdgcn_sched_barrier(0);  // 4 U pair loads in flight at a time, as in interp / compose
 #pragma unroll
-        for (int e = 0; e < U; ++e) wv[d][e] = L[e].value(mn + (size_t)d * nv);
+        for (int e = 0; e < U; ++e) wv[e][d] = L[e].value(mn + (size_t)d * nv);
     }
     if (mphi) {  // the resampled momentum, kept for the backward pass (what interp_forward would have stored)
         R *mo = mphi + (size_t)n * 3 * nv;
@@ -545,7 +497,7 @@ __global__ __launch_bounds__(NT) void ad_star3_tile_kernel(R *__restrict__ out, 
         for (int d = 0; d < 3; ++d)
 #pragma unroll
             for (int e = 0; e < U; ++e)
-                if (q[e].ok) st_pol<LAGO_NT_AD_ST>(&mo[(size_t)d * nv + q[e].s], wv[d][e]);
+                if (q[e].ok) st_pol<LAGO_NT_AD_ST>(&mo[(size_t)d * nv + q[e].s], wv[e][d]);
     }
     __syncthreads();
     const uint32_t sy = (uint32_t)t.P, sx = (uint32_t)t.RY * (uint32_t)t.P;
@@ -566,20 +518,10 @@ __global__ __launch_bounds__(NT) void ad_star3_tile_kernel(R *__restrict__ out, 
     for (int c = 0; c < 3; ++c) {
         R sacc[U];
 #pragma unroll
-        for (int e = 0; e < U; ++e) {
-            R gq[3];
-#pragma unroll
-            for (int d = 0; d < 3; ++d) {
-                gq[d] = (R)0.5f * (fp[c][e][d] - fm[c][e][d]);
-                if (c == d) gq[d] = gq[d] + (R)1.0;
-            }
-            sacc[e] = lg_fma(gq[2], wv[2][e], lg_fma(gq[0], wv[0][e], gq[1] * wv[1][e]));
-        }
+        for (int e = 0; e < U; ++e) sacc[e] = jac_row_dot(c, fp[c][e], fm[c][e], wv[e]);
 #pragma unroll
         for (int e = 0; e < U; ++e)
-            if (q[e].ok) {
-                st_pol<LAGO_NT_AD_ST>(&on[(size_t)c * nv + q[e].s], sacc[e]);
-            }
+            if (q[e].ok) st_pol<LAGO_NT_AD_ST>(&on[(size_t)c * nv + q[e].s], sacc[e]);
     }
 }
 
@@ -589,36 +531,28 @@ std::atomic<int> g_stencil_tile{1};  // 1: LDS row-tile stencil kernels where th
 // workgroups per CU).  Measured against 256 x 2 (2 x 2 rows), 1024 x 2 (4 x 4), 768 x 2, 256 x 4 and 512 x 4 voxels
 // per thread, halo rows by LDS-direct loads, streaming stores and an earlier issue of the first gathers: all within
 // +-3 % or slower (profiles/r03_stencil_tile.md).
-// returns 1 when the shape is left to the other kernels
+// returns kNotTaken when the shape is left to the other kernels
 template <typename R>
 static int ad_star_tile_launch(R *out, R *mphi, const R *phi, const R *m, const Geom &g, int64_t nn, hipStream_t s) {
     constexpr int NT = 512, U = 2, RI = 5;
     RowTile t;
     size_t smem;
-    if (!make_row_tile(t, g, nn, NT * U, NT, 3, (int)sizeof(R), RI, smem)) return 1;
+    if (!make_row_tile(t, g, nn, NT * U, NT, 3, (int)sizeof(R), RI, smem)) return kNotTaken;
+    auto run = [&](auto kernel) {
+        const hipError_t e = launch(kernel, dim3(t.total), dim3(NT), padded_smem(smem), s, out, mphi, phi, m, g, t);
+        if (e != hipSuccess) return fail_hip(e, "ad_star");
+        note_path(LP_STENCIL_TILE);
+        return LAGO_OK;
+    };
     if constexpr (sizeof(R) == 4) {
         // the two benchmark volumes with their geometry compiled in
         const bool cube = g.nx == g.ny && g.ny == g.nz && t.TX == 2 && g_tile_cube;
-        if (cube && g.nz == 128 && t.TY == 4) {
-            const hipError_t e = launch(ad_star3_tile_kernel<R, NT, U, RI, 2, 128>, dim3(t.total), dim3(NT),
-                                        padded_smem(smem), s, out, mphi, phi, m, g, t);
-            if (e != hipSuccess) return fail_hip(e, "ad_star");
-            note_path(LP_STENCIL_TILE);
-            return LAGO_OK;
-        }
-        if (cube && g.nz == 160 && t.TY == 3) {
-            hipLaunchKernelGGL((ad_star3_tile_kernel<R, NT, U, RI, 3, 160>), dim3(t.total), dim3(NT), smem, s, out, mphi, phi, m, g, t);
-            note_path(LP_STENCIL_TILE);
-            return LAGO_OK;
-        }
+        if (cube && g.nz == 128 && t.TY == 4) return run(ad_star3_tile_kernel<R, NT, U, RI, 2, 128>);
+        if (cube && g.nz == 160 && t.TY == 3) return run(ad_star3_tile_kernel<R, NT, U, RI, 3, 160>);
     }
-    if (!with_int<1, 2, 3, 4>((g.nz + 63) / 64, [&](auto ZC) {
-            hipLaunchKernelGGL((ad_star3_tile_kernel<R, NT, U, RI, ZC()>), dim3(t.total), dim3(NT), smem, s, out, mphi, phi,
-                               m, g, t);
-        }))
-        return 1;
-    note_path(LP_STENCIL_TILE);
-    return LAGO_OK;
+    int rc = kNotTaken;
+    with_int<1, 2, 3, 4>((g.nz + 63) / 64, [&](auto ZC) { rc = run(ad_star3_tile_kernel<R, NT, U, RI, ZC()>); });
+    return rc;
 }
 
 template <typename R>
@@ -637,7 +571,7 @@ static int ad_star_impl(R *out, R *mphi, const R *phi, const R *m, int dim, int6
     constexpr int U = 2;
     if (dim == 3 && g_interp_vec && g_stencil_tile && g.nvox >= 4096u) {
         const int rc = ad_star_tile_launch<R>(out, mphi, phi, m, g, nn, s);
-        if (rc != 1) return rc != LAGO_OK ? rc : finish_launch(s, "ad_star");
+        if (rc != kNotTaken) return rc != LAGO_OK ? rc : finish_launch(s, "ad_star");
     }
     uint32_t nbx_u, nb;
     if (dim == 3 && g_interp_vec && slab_grid(g, nn, U, nbx_u, nb)) {

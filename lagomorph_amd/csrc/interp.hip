@@ -82,8 +82,7 @@ __global__ __launch_bounds__(kBlock) void interp_fwd3_unroll_kernel(R *__restric
     const uint32_t qj = (uint32_t)kBlock / (uint32_t)g.nz, rk = (uint32_t)kBlock % (uint32_t)g.nz;  // uniform
 #pragma unroll
     for (int e = 0; e < U; ++e) {
-        // (i, j, k) of slab e: one fast division for e = 0, then +256 voxels per slab as
-        // (+qj rows, +rk voxels) with at most one carry each (host guarantees qj + 1 < ny)
+        // the walk of Slabs<U> (common.hpp), written out: through Slabs this kernel's C = 1 forward measured 2-5 % slower
         if (e == 0) {
             ci = g.dyz.div(s[0]);
             const uint32_t r = s[0] - ci * (uint32_t)(g.ny * g.nz);
@@ -216,23 +215,23 @@ template __global__ void interp3_window_kernel<GW::NT, 8, false, false>(float *,
 
 extern std::atomic<int> g_gather_window;   // fused.hip
 
+// returns kNotTaken when the shape is left to the other kernels
 template <typename R>
-static bool interp_window_launch(R *out, const R *I, const R *u, double dt, int nc, bool bc, const Geom &g, int64_t nn,
-                                 hipStream_t s) {
+static int interp_window_launch(R *out, const R *I, const R *u, double dt, int nc, bool bc, const Geom &g, int64_t nn,
+                                hipStream_t s) {
     if constexpr (sizeof(R) == 4) {
         GWGrid w;
-        if (!make_gwgrid(w, g, nn) || ((uintptr_t)I & 15u)) return false;
+        if (!make_gwgrid(w, g, nn) || ((uintptr_t)I & 15u)) return kNotTaken;
         constexpr int NT = GW::NT, U = 8;
-        const size_t smem = GW::lds_bytes<NT>();
-        const bool unit = unit_dt<R>(dt);
-        with_flags([&](auto UNIT, auto BC) {
-            hipLaunchKernelGGL((interp3_window_kernel<NT, U, UNIT(), BC()>), dim3(w.total), dim3(NT), smem, s, out, I, u,
-                               dt, nc, g, w);
-        }, unit, bc);
+        const hipError_t e = with_flags([&](auto UNIT, auto BC) {
+            return launch(interp3_window_kernel<NT, U, UNIT(), BC()>, dim3(w.total), dim3(NT), GW::lds_bytes<NT>(), s, out,
+                          I, u, dt, nc, g, w);
+        }, unit_dt<R>(dt), bc);
+        if (e != hipSuccess) return fail_hip(e, "interp_forward");
         note_path(LP_GATHER_WINDOW);
-        return true;
+        return LAGO_OK;
     }
-    return false;
+    return kNotTaken;
 }
 
 // ------------------------------------------------------------------ backward, global atomics
@@ -519,9 +518,10 @@ static int interp_forward_impl(R *out, const R *I, const R *u, double dt, int di
     constexpr int U = 2;
     // several channels: through the LDS window (-11 ... -21 % at C = 3); ONE channel does not pay for the window's setup
     // and barrier (81 -> 79 us at 8 x 128^3, slower at 10-voxel deformations and for a broadcast image: tools/ab_interp_window.py)
-    if (dim == 3 && g_interp_vec && g_gather_window && nc >= 2 && g.nvox >= 32768u &&
-        interp_window_launch<R>(out, I, u, dt, (int)nc, bc != 0, g, nn, s))
-        return finish_launch(s, "interp_forward");
+    if (dim == 3 && g_interp_vec && g_gather_window && nc >= 2 && g.nvox >= 32768u) {
+        const int rc = interp_window_launch<R>(out, I, u, dt, (int)nc, bc != 0, g, nn, s);
+        if (rc != kNotTaken) return rc != LAGO_OK ? rc : finish_launch(s, "interp_forward");
+    }
     uint32_t nbx_u, nb;
     if (dim == 3 && g_interp_vec && slab_grid(g, nn, U, nbx_u, nb)) {
         with_flags([&](auto BC, auto UNIT) {

@@ -43,6 +43,10 @@ inline decltype(auto) with_dim(int dim, F &&f) {
 #if defined(__HIPCC__)
 namespace lago {
 
+// What a `*_launch` helper of one kernel family returns (next to LAGO_OK and the error codes, which are <= 0) when the
+// shape is not its own: the entry point then goes on to the next kernel of its ladder.
+constexpr int kNotTaken = 1;
+
 // Launch with `smem` bytes of dynamic LDS.  More than 64 KB has to be allowed per kernel first; a failure to do so is
 // returned (the caller reports it: fail_hip(e, "<entry point>")).  A failure of the launch itself is left to
 // finish_launch, as for every other launch.

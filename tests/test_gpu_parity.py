@@ -569,21 +569,47 @@ def test_fused_fluid_metric_matches_three_call_form(ext, dtype, sp, inverse):
 
 
 @pytest.mark.parametrize("dtype", DTYPES)
-def test_vector_and_scalar_kernels_agree_bitwise(ext, dtype):
-    """The slab-unrolled 3D kernels are a launch-shape choice only."""
+@pytest.mark.parametrize("sp", [(5, 21, 20), (9, 5, 70)])
+def test_vector_and_scalar_kernels_agree_bitwise(ext, dtype, sp):
+    """The slab-unrolled 3D kernels are a launch-shape choice only.  Both shapes pass slab_grid (at least 2048 voxels,
+    256 / nz + 1 < ny) and stay below the row-tile (4096) and LDS-window (32768) thresholds.  (5, 21, 20): a slab is 12
+    rows and 16 voxels on, so the k-, j- and i-carries of the walk all occur, and 2100 = 4 * 512 + 52 voxels leave the
+    last workgroup one partly valid and one wholly invalid slab; (9, 5, 70): 3 rows and 46 voxels per slab."""
     rng = np.random.default_rng(77)
-    sp = (6, 7, 32)
-    I = rnd(rng, (2, 3) + sp, dtype)
+    k = np.float32 if dtype == torch.float32 else np.float64
+    I1, I3 = rnd(rng, (2, 1) + sp, dtype), rnd(rng, (2, 3) + sp, dtype)
     u = _disp(rng, 2, sp, dtype)
     v = rnd(rng, (2, 3) + sp, dtype)
-    a = ext.interp_forward(dev(I), dev(u), 0.9), ext.compose(dev(u), dev(v), -0.3, 1.0)
-    ext.set_vector_kernels(0)
-    try:
-        b = ext.interp_forward(dev(I), dev(u), 0.9), ext.compose(dev(u), dev(v), -0.3, 1.0)
-    finally:
-        ext.set_vector_kernels(1)
-    assert torch.equal(a[0], b[0]) and torch.equal(a[1], b[1])
-    assert_bits(a[0], orc.interp_forward(I, u, 0.9), "vector interp vs oracle")
+    calls = {}   # name -> (call, oracle outputs)
+    for dt in (1.0, 0.9):   # both UNIT instantiations
+        calls[f"interp_forward nc=1 dt={dt}"] = (lambda dt=dt: (ext.interp_forward(dev(I1), dev(u), dt),),
+                                                 (orc.interp_forward(I1, u, dt),))
+        calls[f"interp_forward nc=3 dt={dt}"] = (lambda dt=dt: (ext.interp_forward(dev(I3), dev(u), dt),),
+                                                 (orc.interp_forward(I3, u, dt),))
+        calls[f"compose ds={dt}"] = (lambda ds=dt: (ext.compose(dev(u), dev(v), ds, -0.3),),
+                                     (k(dt) * u + k(-0.3) * orc.interp_forward(v, u, dt),))
+    want_m = orc.interp_forward(v, u, 1.0)
+    calls["Ad_star"] = (lambda: ext.Ad_star(dev(u), dev(v), save_resampled=True),
+                        (orc.jacobian_times_vectorfield_forward(u, want_m, True, False), want_m))
+
+    def took(f):
+        before = ext.path_launches()
+        out = f()
+        after = ext.path_launches()
+        return out, {p: after[p] - before[p] for p in after if after[p] != before[p]}
+
+    for name, (f, want) in calls.items():
+        a, paths = took(f)
+        assert paths == {"vector_gather": 1}, (name, sp, paths)
+        ext.set_vector_kernels(0)
+        try:
+            b, paths = took(f)
+        finally:
+            ext.set_vector_kernels(1)
+        assert paths == {}, (name, sp, paths)
+        for x, y, w in zip(a, b, want):
+            assert torch.equal(x, y), name
+            assert_bits(x, w, f"vector {name} vs oracle")
 
 
 @pytest.mark.parametrize("sp", [(64, 6, 10), (128, 5, 12), (64, 64, 64), (256, 4, 6), (128, 7, 130),
