@@ -139,10 +139,11 @@ inline bool make_geom(Geom &g, int dim, int64_t nn, int64_t nx, int64_t ny, int6
 }
 
 // argument checks that several entry points share
-inline bool overlaps(const void *a, const void *b, size_t bytes) {  // two buffers of `bytes` bytes each
+inline bool overlaps(const void *a, size_t na, const void *b, size_t nb) {  // [a, a + na) and [b, b + nb) bytes
     const uintptr_t p = (uintptr_t)a, q = (uintptr_t)b;
-    return p < q + bytes && q < p + bytes;
+    return p < q + nb && q < p + na;
 }
+inline bool overlaps(const void *a, const void *b, size_t bytes) { return overlaps(a, bytes, b, bytes); }
 inline bool thin(int dim, int64_t nx, int64_t ny, int64_t nz) {  // an extent the central differences cannot take
     return nx <= 1 || ny <= 1 || (dim == 3 && nz <= 1);
 }

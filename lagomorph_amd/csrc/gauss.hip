@@ -6,14 +6,15 @@
 // kernel arguments, no atomics: every element is written once per pass by its own lane, from a sum in a fixed order.
 //
 // Both kernels stage a tile plus its halo in LDS with the border rule applied WHILE LOADING (a wrapped index or a zero),
-// so the filter itself is a plain sliding sum over LDS.  A lane owns four consecutive outputs along the filtered axis and
-// walks its window of 2 H + 4 staged values (H = r rounded up to 4; taps beyond r are zero) four at a time: each staged
-// value is read from LDS once per lane and feeds four fused multiply-adds, (2 H + 4) / 4 LDS reads per output instead of
-// 2 r + 1.
+// so the filter itself is a plain sliding sum over LDS (gauss_slide of gauss.hpp).  A lane owns four consecutive outputs
+// along the filtered axis and walks its window of 2 H + 4 staged values (H = r rounded up to 4; taps beyond r are zero)
+// four at a time: each staged value is read from LDS once per lane and feeds four fused multiply-adds, (2 H + 4) / 4 LDS
+// reads per output instead of 2 r + 1.
 //
 //   gauss_z_kernel   the contiguous axis.  A workgroup stages RT whole row segments (RT x (ZS + 2 H)) with coalesced loads;
 //                    a lane reads its window as aligned 4-vectors (lanes 16 / 32 bytes apart: conflict-free) and stores
-//                    one 4-vector.
+//                    one 4-vector.  The pass itself is gauss_z_pass of gauss.hpp (one field, one sum; lncc.hip
+//                    instantiates it with two and five): this kernel adds the alpha / accumulate store.
 //   gauss_s_kernel   a strided axis (y: stride nz, x: stride ny nz).  Lanes run along the contiguous direction, so every
 //                    global access is a coalesced 256-byte row; the workgroup stages a (T + 2 H) x 64 slab and a lane walks
 //                    it down its own column (consecutive lanes, consecutive banks).
@@ -21,44 +22,9 @@
 // A pass whose workgroups each stage the WHOLE extent of their lines (one z segment per row, one axis tile per column)
 // reads everything it needs before its barrier and writes after it, and no other workgroup touches those lines: such a
 // pass may run in place.  The three-pass accumulate form uses that (see gauss_impl).
-#include "gauss.hpp"   // GaussTaps, GaussPass, gauss_resolve, gauss_plan: shared with lncc.hip
+#include "gauss.hpp"   // the descriptors, the plan, gauss_slide and gauss_z_pass: shared with lncc.hip
 
 namespace lago {
-
-// The sliding sum of one lane: four outputs from the 2 H + 4 staged values at win[0], win[STRIDE], ...  Output o sits at
-// window position H + o, so value j carries tap j - H - o.  Taps are wave-uniform (kernel arguments, uniform index).
-template <typename R, typename LOAD4>
-__device__ __forceinline__ void gauss_slide(const GaussTaps &taps, int H, LOAD4 load4, double (&acc)[4]) {
-    double t[7];   // taps of k0 - 3 .. k0 + 3 for the four values at window offsets k0 .. k0 + 3 (relative to output 0)
-#pragma unroll
-    for (int j = 0; j < 3; ++j) t[j + 4] = 0.0;   // k = -H-3 .. -H-1: beyond every radius
-#pragma unroll
-    for (int o = 0; o < 4; ++o) acc[o] = 0.0;
-    if (H == 0) {   // radius 0 (the copy pass): the values themselves, no product with a zero tap (0 * inf), -0 kept
-        R v[4];
-        load4(0, v);
-#pragma unroll
-        for (int o = 0; o < 4; ++o) acc[o] = (double)v[o];
-        return;
-    }
-    const int steps = (2 * H + 4) >> 2;
-    for (int s = 0; s < steps; ++s) {
-        const int k0 = 4 * s - H;
-#pragma unroll
-        for (int j = 0; j < 3; ++j) t[j] = t[j + 4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const int k = k0 + j;
-            t[j + 3] = taps.w[k < 0 ? -k : k];
-        }
-        R v[4];
-        load4(4 * s, v);
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-#pragma unroll
-            for (int o = 0; o < 4; ++o) acc[o] = lg_fma(t[i - o + 3], (double)v[i], acc[o]);
-    }
-}
 
 template <typename R>
 __device__ __forceinline__ R gauss_epilogue(const GaussPass &p, R alpha, double dsum, R prev) {
@@ -68,73 +34,34 @@ __device__ __forceinline__ R gauss_epilogue(const GaussPass &p, R alpha, double 
     return p.accumulate ? prev + val : val;   // (accumulate is set on the last pass only)
 }
 
-extern __shared__ __attribute__((aligned(32))) unsigned char gauss_smem[];
-
 template <typename R>
 __global__ __launch_bounds__(kBlock) void gauss_z_kernel(R *out, const R *in, GaussTaps taps, R alpha, GaussPass p) {
     typedef R vec4 __attribute__((ext_vector_type(4)));
-    R *lds = reinterpret_cast<R *>(gauss_smem);
-    const uint32_t rb = p.dseg.div(blockIdx.x);
-    const uint32_t seg = blockIdx.x - rb * p.nseg;
-    const uint64_t row0 = (uint64_t)rb * p.RT;
-    const int zs0 = (int)(seg * p.ZS);
-    const int lo = p.H - p.r, hi = p.H + (int)p.ZS + p.r;   // staged positions outside [lo, hi) carry zero taps only
-    const uint32_t staged = p.RT * p.pitch;
-    for (uint32_t e0 = threadIdx.x; e0 < staged; e0 += kGaussInFlight * kBlock) {   // loads first, then the LDS stores
-        R val[kGaussInFlight];
-#pragma unroll
-        for (int f = 0; f < kGaussInFlight; ++f) {
-            const uint32_t e = e0 + (uint32_t)f * kBlock;
-            const uint32_t rl = p.dpitch.div(e);
-            const int q = (int)(e - rl * p.pitch);
-            const uint64_t row = row0 + rl;
-            val[f] = (R)0;
-            if (e < staged && row < p.outer && q >= lo && q < hi) {
-                bool inside;
-                const uint32_t u = gauss_resolve<R>(p, zs0 - p.H + q, inside);
-                if (inside) val[f] = in[row * p.n + u];
-            }
+    const R *const fields[1] = {in};
+    gauss_z_pass<R, 1, 1>(reinterpret_cast<R *>(gauss_smem), fields, taps, p,
+                          [](const double (&v)[1], double (&x)[1]) { x[0] = v[0]; },
+                          [&](uint64_t row, uint32_t z0, const double (&acc)[1][4]) {
+        R *o = out + row * p.n + z0;
+        if (p.vec && z0 + 3u < p.n) {
+            vec4 x = {(R)0, (R)0, (R)0, (R)0};
+            if (p.accumulate) x = *reinterpret_cast<const vec4 *>(o);
+            x.x = gauss_epilogue<R>(p, alpha, acc[0][0], x.x);
+            x.y = gauss_epilogue<R>(p, alpha, acc[0][1], x.y);
+            x.z = gauss_epilogue<R>(p, alpha, acc[0][2], x.z);
+            x.w = gauss_epilogue<R>(p, alpha, acc[0][3], x.w);
+            *reinterpret_cast<vec4 *>(o) = x;
+            return;
         }
+        R prev[4] = {(R)0, (R)0, (R)0, (R)0};
+        if (p.accumulate) {
 #pragma unroll
-        for (int f = 0; f < kGaussInFlight; ++f) {
-            const uint32_t e = e0 + (uint32_t)f * kBlock;
-            if (e < staged) lds[e] = val[f];
+            for (int k = 0; k < 4; ++k)
+                if (z0 + (uint32_t)k < p.n) prev[k] = o[k];
         }
-    }
-    __syncthreads();
-    const uint32_t item = threadIdx.x;
-    if (item >= p.RT * p.nzc) return;
-    const uint32_t rl = p.dzc.div(item);
-    const uint32_t c = item - rl * p.nzc;
-    const uint64_t row = row0 + rl;
-    const uint32_t z0 = (uint32_t)zs0 + 4u * c;
-    if (row >= p.outer || z0 >= p.n) return;
-    const R *win = lds + rl * p.pitch + 4u * c;
-    double acc[4];
-    gauss_slide<R>(taps, p.H, [&](int off, R (&v)[4]) {
-        const vec4 x = *reinterpret_cast<const vec4 *>(win + off);
-        v[0] = x.x; v[1] = x.y; v[2] = x.z; v[3] = x.w;
-    }, acc);
-    R *o = out + row * p.n + z0;
-    if (p.vec && z0 + 3u < p.n) {
-        vec4 x = {(R)0, (R)0, (R)0, (R)0};
-        if (p.accumulate) x = *reinterpret_cast<const vec4 *>(o);
-        x.x = gauss_epilogue<R>(p, alpha, acc[0], x.x);
-        x.y = gauss_epilogue<R>(p, alpha, acc[1], x.y);
-        x.z = gauss_epilogue<R>(p, alpha, acc[2], x.z);
-        x.w = gauss_epilogue<R>(p, alpha, acc[3], x.w);
-        *reinterpret_cast<vec4 *>(o) = x;
-        return;
-    }
-    R prev[4] = {(R)0, (R)0, (R)0, (R)0};
-    if (p.accumulate) {
 #pragma unroll
         for (int k = 0; k < 4; ++k)
-            if (z0 + (uint32_t)k < p.n) prev[k] = o[k];
-    }
-#pragma unroll
-    for (int k = 0; k < 4; ++k)
-        if (z0 + (uint32_t)k < p.n) o[k] = gauss_epilogue<R>(p, alpha, acc[k], prev[k]);
+            if (z0 + (uint32_t)k < p.n) o[k] = gauss_epilogue<R>(p, alpha, acc[0][k], prev[k]);
+    });
 }
 
 template <typename R>
@@ -179,11 +106,11 @@ __global__ __launch_bounds__(kBlock) void gauss_s_kernel(R *out, const R *in, Ga
         const uint32_t a = (uint32_t)a0 + 4u * c;
         if (a >= p.n) break;
         const R *win = lds + (size_t)(4u * c) * kGaussLanes + lane;
-        double acc[4];
-        gauss_slide<R>(taps, p.H, [&](int off, R (&v)[4]) {
+        double acc[1][4];
+        gauss_slide<R, 1, 1>(taps, p.H, [&](int off, R (&v)[1][4]) {
 #pragma unroll
-            for (int i = 0; i < 4; ++i) v[i] = win[(off + i) * kGaussLanes];
-        }, acc);
+            for (int i = 0; i < 4; ++i) v[0][i] = win[(off + i) * kGaussLanes];
+        }, [](const double (&v)[1], double (&x)[1]) { x[0] = v[0]; }, acc);
         R *o = dst + (size_t)a * p.inner + ii;
         R prev[4] = {(R)0, (R)0, (R)0, (R)0};
         if (p.accumulate) {
@@ -193,50 +120,30 @@ __global__ __launch_bounds__(kBlock) void gauss_s_kernel(R *out, const R *in, Ga
         }
 #pragma unroll
         for (int k = 0; k < 4; ++k)
-            if (a + (uint32_t)k < p.n) o[(size_t)k * p.inner] = gauss_epilogue<R>(p, alpha, acc[k], prev[k]);
+            if (a + (uint32_t)k < p.n) o[(size_t)k * p.inner] = gauss_epilogue<R>(p, alpha, acc[0][k], prev[k]);
     }
-}
-
-template <typename R>
-static uint32_t gauss_blocks(const GaussPass &p, int axis) {
-    if (axis == 2) return (uint32_t)((p.outer + p.RT - 1) / p.RT * p.nseg);
-    return (uint32_t)(p.outer * p.nat * p.nit);
 }
 
 // whether every workgroup of the pass stages the whole extent of its lines: the pass may then run in place
 static bool gauss_whole_lines(const GaussPass &p, int axis) { return axis == 2 ? p.nseg == 1 : p.nat == 1; }
 
 template <typename R>
-static void gauss_launch(const GaussPass &p, int axis, R *dst, const R *src, const GaussTaps &taps, R alpha,
-                         hipStream_t s) {
-    const uint32_t nb = gauss_blocks<R>(p, axis);
-    if (axis == 2) {
-        const size_t smem = (size_t)p.RT * p.pitch * sizeof(R);
-        hipLaunchKernelGGL((gauss_z_kernel<R>), dim3(nb), dim3(kBlock), smem, s, dst, src, taps, alpha, p);
-    } else {
-        const size_t smem = (size_t)(p.T + 2u * (uint32_t)p.H) * kGaussLanes * sizeof(R);
-        hipLaunchKernelGGL((gauss_s_kernel<R>), dim3(nb), dim3(kBlock), smem, s, dst, src, taps, alpha, p);
-    }
+static hipError_t gauss_launch(const GaussPass &p, int axis, R *dst, const R *src, const GaussTaps &taps, R alpha,
+                               hipStream_t s) {
+    size_t smem;
+    const uint32_t nb = gauss_blocks<R>(p, axis, 1, smem);
+    return launch(axis == 2 ? gauss_z_kernel<R> : gauss_s_kernel<R>, dim3(nb), dim3(kBlock), smem, s, dst, src, taps,
+                  alpha, p);
 }
 
 template <typename R>
 static int gauss_impl(R *out, const R *in, R *scratch, const int *radii, const double *taps, int mode, double alpha,
                       int accumulate, int dim, int64_t rows, int64_t nx, int64_t ny, int64_t nz, void *stream) {
-    if (dim != 2 && dim != 3) return fail_invalid("Only two- and three-dimensional gaussian smoothing is supported");
-    if (mode != LAGO_GAUSS_WRAP && mode != LAGO_GAUSS_ZERO)
-        return fail_invalid("gaussian_smooth: unknown border mode %d", mode);
-    if (!radii) return fail_invalid("gaussian_smooth: null radii");
-    int rad[3] = {0, 0, 0};   // per axis of the (nx, ny, nz) geometry; a 2D field is (1, H, W)
-    const double *tp[3] = {nullptr, nullptr, nullptr};
-    for (int a = 0; a < dim; ++a) {
-        const int r = radii[a];
-        if (r < 0 || r > kGaussMaxRadius)
-            return fail_invalid("gaussian_smooth: radius %d is outside 0..%d (wider kernels: use the FFT operator)", r,
-                                kGaussMaxRadius);
-        if (r > 0 && !taps) return fail_invalid("gaussian_smooth: null taps");
-        rad[a + 3 - dim] = r;
-        tp[a + 3 - dim] = taps ? taps + (size_t)a * (kGaussMaxRadius + 1) : nullptr;
-    }
+    int rad[3];
+    const double *tp[3];
+    const int rc = gauss_parse_axes("gaussian_smooth", "gaussian smoothing", " (wider kernels: use the FFT operator)", dim,
+                                    mode, radii, taps, rad, tp);
+    if (rc != LAGO_OK) return rc;
     Geom g;
     if (!make_geom(g, dim, rows, nx, ny, nz)) return fail_invalid("gaussian_smooth: bad extent");
     if (g.nblocks == 0) return LAGO_OK;
@@ -294,26 +201,27 @@ static int gauss_impl(R *out, const R *in, R *scratch, const int *radii, const d
         p.final = last;
         p.accumulate = last && accumulate;
         if (dst == scratch) p.vec = p.vec && scratch_vec;
-        gauss_launch<R>(p, order[i], dst, src, tw[i], al, s);
+        const hipError_t e = gauss_launch<R>(p, order[i], dst, src, tw[i], al, s);
+        if (e != hipSuccess) return fail_hip(e, "gaussian_smooth");
         src = dst;
     }
     return finish_launch(s, "gaussian_smooth");
 }
 
 template <typename R>
-bool gauss_axis_pass(R *dst, const R *src, int axis, int r, const double *half, int mode, int64_t rows, const Geom &g,
-                     hipStream_t s) {
+int gauss_axis_pass(const char *name, R *dst, const R *src, int axis, int r, const double *half, int mode, int64_t rows,
+                    const Geom &g, hipStream_t s) {
     GaussPass p;
     GaussTaps tw;
-    if (!gauss_plan<R>(p, axis, r, mode, rows, g, dst)) return false;
+    if (!gauss_plan<R>(p, axis, r, mode, rows, g, dst)) return fail_invalid("%s: bad extent", name);
     gauss_fill_taps<R>(tw, r, half);
-    gauss_launch<R>(p, axis, dst, src, tw, (R)1, s);   // (final = 0: the epilogue returns the rounded sum as it is)
-    return true;
+    const hipError_t e = gauss_launch<R>(p, axis, dst, src, tw, (R)1, s);   // (final = 0: the rounded sum as it is)
+    return e != hipSuccess ? fail_hip(e, name) : LAGO_OK;
 }
-template bool gauss_axis_pass<float>(float *, const float *, int, int, const double *, int, int64_t, const Geom &,
-                                     hipStream_t);
-template bool gauss_axis_pass<double>(double *, const double *, int, int, const double *, int, int64_t, const Geom &,
-                                      hipStream_t);
+template int gauss_axis_pass<float>(const char *, float *, const float *, int, int, const double *, int, int64_t,
+                                    const Geom &, hipStream_t);
+template int gauss_axis_pass<double>(const char *, double *, const double *, int, int, const double *, int, int64_t,
+                                     const Geom &, hipStream_t);
 
 }  // namespace lago
 

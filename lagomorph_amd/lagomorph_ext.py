@@ -544,23 +544,7 @@ def gaussian_smooth_forward(x, radii, taps, mode, alpha=1.0, out=None, accumulat
     dim, nx, ny, nz = _spatial(x)
     if dim not in (2, 3):
         raise RuntimeError("Only two- and three-dimensional gaussian smoothing is supported")
-    if mode not in GAUSS_MODES:
-        raise ValueError(f"gaussian_smooth: unknown mode {mode!r} (one of {sorted(GAUSS_MODES)})")
-    radii = [int(r) for r in radii]
-    if len(radii) != dim or len(taps) != dim:
-        raise ValueError(f"gaussian_smooth: {dim} radii and tap vectors are needed, one per spatial axis")
-    half = (ctypes.c_double * (dim * (GAUSS_MAX_RADIUS + 1)))()
-    for a, r in enumerate(radii):
-        if r < 0 or r > GAUSS_MAX_RADIUS:
-            raise ValueError(f"gaussian_smooth: radius {r} on axis {a} is outside 0..{GAUSS_MAX_RADIUS}")
-        if r > 0:
-            t = [float(v) for v in taps[a]]
-            if len(t) != 2 * r + 1:
-                raise ValueError(f"gaussian_smooth: axis {a} needs {2 * r + 1} taps, got {len(t)}")
-            if any(t[r + k] != t[r - k] for k in range(1, r + 1)):
-                raise ValueError("gaussian_smooth: the taps must be symmetric")
-            for k in range(r + 1):
-                half[a * (GAUSS_MAX_RADIUS + 1) + k] = t[r + k]
+    radii, half = _gauss_half_taps("gaussian_smooth", dim, radii, taps, mode)
     if accumulate and out is None:
         raise RuntimeError("gaussian_smooth: accumulate needs out")
     if not x.is_cuda:
@@ -591,7 +575,7 @@ def gaussian_smooth_forward(x, radii, taps, mode, alpha=1.0, out=None, accumulat
 
 
 def _gauss_half_taps(what, dim, radii, taps, mode):
-    """The radius / tap checks of gaussian_smooth_forward: (radii as ints, the half-tap block lago_gauss_smooth takes)."""
+    """The mode / radius / tap checks of the entry point `what`: (radii as ints, the half-tap block lago_gauss_smooth takes)."""
     if mode not in GAUSS_MODES:
         raise ValueError(f"{what}: unknown mode {mode!r} (one of {sorted(GAUSS_MODES)})")
     radii = [int(r) for r in radii]

@@ -219,6 +219,72 @@ def test_rows_longer_than_one_segment(lm, dtype):
     assert max(u) <= 1.0, u
 
 
+# ---- 4b. the moments pass IS the z pass of gaussian_smooth (csrc/gauss.hpp: gauss_z_pass, two instantiations)
+
+def _taps(lm, radii):
+    """Per axis the 2 r + 1 taps of radius r (sigma = r / 4 at truncate 4 gives exactly r; [1.] for r = 0)."""
+    taps = [lm.gaussian_taps(r / 4.0) for r in radii]
+    assert [(len(t) - 1) // 2 for t in taps] == list(radii)
+    return taps
+
+
+def _off_by_one(t):
+    """The values of t in a contiguous view whose storage starts one element (4 / 8 bytes) off the vector alignment."""
+    flat = torch.empty(t.numel() + 1, dtype=t.dtype, device=t.device)
+    v = flat[1:].view(t.shape)
+    v.copy_(t)
+    assert v.is_contiguous() and v.data_ptr() % 16 != 0
+    return v
+
+
+@pytest.mark.parametrize("mode", MODES)
+@pytest.mark.parametrize("dtype", DTYPES)
+def test_z_only_moments_are_the_z_pass_of_gaussian_smooth(lm, dtype, mode):
+    """Radii 0 on the other axes: moments[0] and moments[1] are gaussian_smooth_forward of I and J, bit for bit.  The
+    shapes: a short last 4-group with masked scalar stores; vector stores; two segments with the halo across the segment
+    edge; 32 rows per workgroup with a ragged last row block; 2D.  Radii 1, 4, 9 are H = 4, 4, 12, and 9 on extent 7
+    wraps more than once.  Each case also runs on inputs one element off the vector alignment, with gaussian_smooth
+    writing into an `out` that is off as well (its scalar stores; the moments tensor is always allocated aligned, so the
+    scalar stores of that kernel are those of the extent 7 case)."""
+    from lagomorph_amd import lagomorph_ext as ext
+
+    for n, shape in enumerate(((1, 2, 3, 5, 7), (2, 1, 2, 3, 64), (1, 1, 2, 2, 1030), (1, 33, 1, 1, 8), (1, 1, 6, 9))):
+        I, J = normal(shape, 60 + 2 * n, dtype), normal(shape, 61 + 2 * n, dtype)
+        for r in (1, 4, 9):
+            radii = [0] * (len(shape) - 3) + [r]
+            taps = _taps(lm, radii)
+            want = [ext.gaussian_smooth_forward(x, radii, taps, mode) for x in (I, J)]
+            mom = ext.lncc_moments(I, J, radii, taps, mode)
+            assert mom.shape == (5,) + shape
+            assert torch.equal(mom[0], want[0]) and torch.equal(mom[1], want[1]), (shape, r)
+            oI, oJ = _off_by_one(I), _off_by_one(J)
+            off = ext.lncc_moments(oI, oJ, radii, taps, mode)
+            assert torch.equal(off, mom), (shape, r)
+            for x, w in zip((oI, oJ), want):
+                out = _off_by_one(torch.zeros_like(x))
+                assert ext.gaussian_smooth_forward(x, radii, taps, mode, out=out) is out
+                assert torch.equal(out, w), (shape, r)
+
+
+@pytest.mark.parametrize("mode", MODES)
+@pytest.mark.parametrize("dtype", DTYPES)
+def test_copy_moments_then_x_and_y_are_gaussian_smooth_of_the_products(lm, dtype, mode):
+    """z radius 0, x and / or y filtered: the copy pass rounds each exact double product once and both paths then run x
+    before y, so all five moments are gaussian_smooth_forward of I, J and the products formed the same way.  70 > 64 gives
+    two axis tiles in float32."""
+    from lagomorph_amd import lagomorph_ext as ext
+
+    for n, shape in enumerate(((1, 2, 5, 6, 7), (1, 1, 70, 3, 8))):
+        I, J = normal(shape, 80 + 2 * n, dtype), normal(shape, 81 + 2 * n, dtype)
+        a, b = I.double(), J.double()
+        fields = (I, J, (a * a).to(dtype), (a * b).to(dtype), (b * b).to(dtype))
+        for radii in ((2, 0, 0), (0, 3, 0), (2, 3, 0)):
+            taps = _taps(lm, radii)
+            mom = ext.lncc_moments(I, J, list(radii), taps, mode)
+            for m, x in enumerate(fields):
+                assert torch.equal(mom[m], ext.gaussian_smooth_forward(x, list(radii), taps, mode)), (shape, radii, m)
+
+
 # ---- 5. graph capture
 
 def test_graph_capture_of_forward_and_backward(lm):
