@@ -38,7 +38,7 @@ FLAGS = [
 
 
 def _deps():
-    return [os.path.join(CSRC, h) for h in ("common.hpp", "launch.hpp", "gauss.hpp", "fft_lds.hpp", "fft3_sizes.hpp", "stencil_tile.hpp", "gather_window.hpp", "fluid_bin.hpp", "affine_box.hpp")] + [
+    return [os.path.join(CSRC, h) for h in ("common.hpp", "launch.hpp", "gauss.hpp", "fft_lds.hpp", "fft3_sizes.hpp", "stencil_tile.hpp", "gather_window.hpp", "splat_window.hpp", "fluid_bin.hpp", "affine_box.hpp")] + [
         os.path.join(HERE, "..", "include", "lagomorph_hip.h")]
 
 

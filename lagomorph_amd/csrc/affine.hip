@@ -15,6 +15,7 @@
 #include <algorithm>
 
 #include "common.hpp"
+#include "splat_window.hpp"   // lds_add, flipped_weights, flush_row
 #include "affine_box.hpp"   // half_extent, the box kernel's candidate / ownership functions
 
 #ifndef LAGO_NT_AFFINE_ST
@@ -284,35 +285,21 @@ __global__ __launch_bounds__(kBlock) void affine_splat_box_kernel(R *__restrict_
                     const uint32_t lx1 = (uint32_t)(clamp1(fx[q] + 1, nx) - X0), ly1 = (uint32_t)(clamp1(fy[q] + 1, ny) - Y0),
                                    lz1 = (uint32_t)(clamp1(fz[q] + 1, nz) - Z0);
                     const uint32_t cxs[2] = {lx[q], lx1}, cys[2] = {ly[q], ly1}, czs[2] = {lz[q], lz1};
-                    // sequentially flipped weights (include/interp.h:431-453): x outer, y, z inner
-                    R ddx = (R)1.f - (hx[q] - (R)fx[q]), ddy = (R)1.f - (hy[q] - (R)fy[q]), ddz = (R)1.f - (hz[q] - (R)fz[q]);
+                    R w[8];
+                    flipped_weights(w, (R)1.f - (hx[q] - (R)fx[q]), (R)1.f - (hy[q] - (R)fy[q]), (R)1.f - (hz[q] - (R)fz[q]), diff[q]);
 #pragma unroll
-                    for (int c8 = 0; c8 < 8; ++c8) {
-                        const R w = (ddx * ddy * ddz) * diff[q];
-                        __hip_atomic_fetch_add(win + ((cxs[c8 >> 2] * (uint32_t)WY + cys[(c8 >> 1) & 1]) * (uint32_t)WZ + czs[c8 & 1]),
-                                               (double)w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                        ddz = (R)1.f - ddz;
-                        if (c8 & 1) ddy = (R)1.f - ddy;
-                        if ((c8 & 3) == 3) ddx = (R)1.f - ddx;
-                    }
+                    for (int c8 = 0; c8 < 8; ++c8)
+                        lds_add(win + ((cxs[c8 >> 2] * (uint32_t)WY + cys[(c8 >> 1) & 1]) * (uint32_t)WZ + czs[c8 & 1]), (double)w[c8]);
                 }
             }
         }
         __syncthreads();
-        // flush: one wave per window row (lx, ly), lanes along z; re-zero for the next channel
+        // flush, window row (lx, ly) by row; re-zero for the next channel
         R *dIc = dIn + (size_t)c * nv;
         const int fx_n = min(ex + 1, nx - X0), fy_n = min(ey + 1, ny - Y0), fz_n = min(ez + 1, nz - Z0);
         for (int row = wave; row < fx_n * fy_n; row += kBlock / 64) {
             const int lx = row / fy_n, ly = row % fy_n;
-            double *wrow = win + (lx * WY + ly) * WZ;
-            R *grow = dIc + ((size_t)(X0 + lx) * ny + (Y0 + ly)) * nz + Z0;
-            for (int lz = lane; lz < fz_n; lz += 64) {
-                const double acc = wrow[lz];
-                if (acc != 0.0) {
-                    wrow[lz] = 0.0;
-                    atomic_add(grow + lz, (R)acc);
-                }
-            }
+            flush_row<true>(win + (lx * WY + ly) * WZ, dIc + ((size_t)(X0 + lx) * ny + (Y0 + ly)) * nz + Z0, fz_n);
         }
         __syncthreads();
     }

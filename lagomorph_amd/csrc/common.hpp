@@ -383,6 +383,16 @@ __device__ __forceinline__ R lerp3_pairs(const R (&lo)[4], const R (&hi)[4], R t
     return lg_fma(omv, f_hi ? ghi : glo, v * (c_lo ? glo : ghi));
 }
 
+// The position gradient of the trilinear value (include/interp.h:315-326) from the eight corner values v0..v7, for
+// Lerp3::grad and the sheared splat kernels.
+template <typename R>
+__device__ __forceinline__ void lerp3_grad(const R (&c)[8], R t, R u, R v, R &gx, R &gy, R &gz) {
+    const R omt = (R)1.f - t, omu = (R)1.f - u, omv = (R)1.f - v;
+    gx = lg_fma(omv, lg_fma(omu, c[1] - c[0], u * (c[2] - c[3])), v * lg_fma(omu, c[5] - c[4], u * (c[6] - c[7])));
+    gy = lg_fma(omv, lg_fma(omt, c[3] - c[0], t * (c[2] - c[1])), v * lg_fma(omt, c[7] - c[4], t * (c[6] - c[5])));
+    gz = lg_fma(omu, lg_fma(omt, c[4] - c[0], t * (c[5] - c[1])), u * lg_fma(omt, c[7] - c[3], t * (c[6] - c[2])));
+}
+
 // Trilinear stencil.  The 8 corners are 4 (x, y) rows times the z pair
 // (floor, floor+1), which is contiguous in memory: each row is fetched with ONE
 // pair load at z = zb = min(clamped floor, nz-2); when the sample lies beyond a z
@@ -459,14 +469,10 @@ struct Lerp3 {
         return lg_fma(omv, lg_fma(omu, lg_fma(omt, c[0], t * c[1]), u * lg_fma(omt, c[3], t * c[2])),
                       v * lg_fma(omu, lg_fma(omt, c[4], t * c[5]), u * lg_fma(omt, c[7], t * c[6])));
     }
-    // include/interp.h:315-326
     __device__ __forceinline__ void grad(const R *__restrict__ img, R &gx, R &gy, R &gz) const {
         R c[8];
         fetch(img, c);
-        const R omt = (R)1.f - t, omu = (R)1.f - u, omv = (R)1.f - v;
-        gx = lg_fma(omv, lg_fma(omu, c[1] - c[0], u * (c[2] - c[3])), v * lg_fma(omu, c[5] - c[4], u * (c[6] - c[7])));
-        gy = lg_fma(omv, lg_fma(omt, c[3] - c[0], t * (c[2] - c[1])), v * lg_fma(omt, c[7] - c[4], t * (c[6] - c[5])));
-        gz = lg_fma(omu, lg_fma(omt, c[4] - c[0], t * (c[5] - c[1])), u * lg_fma(omt, c[7] - c[3], t * (c[6] - c[2])));
+        lerp3_grad(c, t, u, v, gx, gy, gz);
     }
 };
 

@@ -7,6 +7,7 @@
 // wavefront rows, the 8 (4) lerp corners are gathers served by L1/L2.
 #include "common.hpp"
 #include "gather_window.hpp"
+#include "splat_window.hpp"   // lds_add (2D window splat)
 
 #ifndef LAGO_NT_INTERPW_LD
 #define LAGO_NT_INTERPW_LD 1   // u of the window kernel (C >= 2) is read once: interp_forward C = 3 148 -> 131 us
@@ -414,7 +415,7 @@ __global__ __launch_bounds__(kS2T) void splat2d_lds_kernel(R *__restrict__ d_I, 
             for (int q = 0; q < 4; ++q) {
                 const R w = S[e].w[q] * diff;                      // include/interp.h:404-424
                 if (wl[e][q] != NOWIN)
-                    __hip_atomic_fetch_add(win + wl[e][q], (double)w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                    lds_add(win + wl[e][q], (double)w);
                 else
                     atomic_add(dIc + S[e].o[q], w);
             }
@@ -427,7 +428,8 @@ __global__ __launch_bounds__(kS2T) void splat2d_lds_kernel(R *__restrict__ d_I, 
             }
         }
         __syncthreads();
-        // flush: one wave per window row, lanes along the row
+        // flush: one wave per window row, lanes along the row.  (Its own copy of flush_row, splat_window.hpp: through the
+        // shared form the NEED_U instantiations take 88 SGPRs instead of 87, profiles/splat_frame_refactor.md)
         {
             const int lane = threadIdx.x & 63;
             const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));

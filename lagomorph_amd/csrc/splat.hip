@@ -33,7 +33,11 @@
 // same pass: the thread that owns a voxel owns its d_u entries, so the channel
 // sum is a plain read-modify-write in ascending channel order, bit-identical to
 // the reference's thread-owned accumulation.
-#include "common.hpp"
+//
+// What these kernels share with each other and with the other LDS-window splats (tile decode, flipped weights, the
+// sheared window's placement, adds, clamped atomics and flush, the row flush) is in splat_window.hpp; the gradient
+// expressions are lerp3_grad (common.hpp).
+#include "splat_window.hpp"
 
 #ifndef LAGO_NT_SPLAT_LD
 #define LAGO_NT_SPLAT_LD 1   // grad_out and u of the C = 1 sheared splat are read once: -1.9 % (profiles/r04_cache_policy.md)
@@ -79,10 +83,6 @@ struct TileGeom {
 
 // TX TY TZ(0 = auto) window margins MX MY MZ around the probed origin, threads per workgroup
 static KnobArray<7> g_tile_cfg({0, 8, 0, 1, 1, 4, 512});
-
-__device__ __forceinline__ void lds_add(double *p, double v) {
-    __hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-}
 
 template <typename R, int N>
 struct alignas(sizeof(R) * N) SVec {
@@ -130,16 +130,7 @@ __global__ __launch_bounds__(NT) void splat_tiled_kernel(R *__restrict__ d_I, R 
     const double dt = pa.dt;
     constexpr bool DISP = MODE == POS_DISP || MODE == POS_DISP_UNIT;
 
-    // workgroup -> (batch item, tile)
-    const uint32_t L = block_order(blockIdx.x, tg.total, tg.rev);
-    const uint32_t n = tg.d_tiles.div(L);
-    uint32_t r = L - n * tg.tiles_per_item;
-    const uint32_t bx = tg.d_tyz.div(r);
-    r -= bx * (tg.nty * tg.ntz);
-    const uint32_t by = tg.d_tz.div(r);
-    const uint32_t bz = r - by * tg.ntz;
-    const int x0 = bx * tg.TX, y0 = by * tg.TY, z0 = bz * tg.TZ;
-    const int ex = min(tg.TX, snx - x0), ey = min(tg.TY, sny - y0), ez = min(tg.TZ, snz - z0);
+    const auto [n, x0, y0, z0, ex, ey, ez] = tile_at(tg, snx, sny, snz);   // workgroup -> (batch item, tile)
 
     const R *un = DISP ? static_cast<const R *>(pa.u) + (size_t)n * 3 * snv : nullptr;
     const R *An = MODE == POS_AFFINE ? static_cast<const R *>(pa.A) + (size_t)n * 9 : nullptr;
@@ -194,16 +185,7 @@ __global__ __launch_bounds__(NT) void splat_tiled_kernel(R *__restrict__ d_I, R 
         const R dy = (R)1.f - (hy - (R)fy);
         const R dz = (R)1.f - (hz - (R)fz);
         R wgt[8];
-        {
-            R ddx = dx, ddy = dy, ddz = dz;
-#pragma unroll
-            for (int q = 0; q < 8; ++q) {
-                wgt[q] = (ddx * ddy * ddz) * diff;
-                ddz = (R)1.f - ddz;
-                if (q & 1) ddy = (R)1.f - ddy;
-                if ((q & 3) == 3) ddx = (R)1.f - ddx;
-            }
-        }
+        flipped_weights(wgt, dx, dy, dz, diff);
         const bool interior = (unsigned)(fx - ilox) < (unsigned)ispx && (unsigned)(fy - iloy) < (unsigned)ispy &&
                               (unsigned)(fz - iloz) < (unsigned)ispz;
         if (interior) {
@@ -232,20 +214,13 @@ __global__ __launch_bounds__(NT) void splat_tiled_kernel(R *__restrict__ d_I, R 
             }
         }
     };
-    // flush touched cells: one wave per window row (lx, ly) -- the row decode and both base
-    // addresses are wave-uniform (scalar), the lanes run along z
+    // flush touched cells: one wave per window row (lx, ly)
     auto flush = [&](R *dIc) {
-        const int lane = threadIdx.x & 63;
         const uint32_t wv = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
         const uint32_t nrows = (uint32_t)(wex * wey);
         for (uint32_t row = wv; row < nrows; row += NT / 64) {
             const uint32_t lx = tg.d_wey.div(row), ly = row - lx * (uint32_t)wey;
-            const double *wrow = win + (lx * (uint32_t)WY + ly) * (uint32_t)WZ;
-            R *grow = dIc + ((size_t)(wx0 + lx) * ny + (wy0 + ly)) * nz + wz0;
-            for (int lz = lane; lz < wez; lz += 64) {
-                const double acc = wrow[lz];
-                if (acc != 0.0) atomic_add(grow + lz, (R)acc);
-            }
+            flush_row<false>(win + (lx * (uint32_t)WY + ly) * (uint32_t)WZ, dIc + ((size_t)(wx0 + lx) * ny + (wy0 + ly)) * nz + wz0, wez);
         }
     };
 
@@ -406,17 +381,7 @@ __global__ __launch_bounds__(NT) void splat_tiled_kernel(R *__restrict__ d_I, R 
 //  * what still misses the window takes the reference's clamped global atomics, corner by corner.
 // Arithmetic (positions, sequentially flipped weights, gradient expressions) is that of the kernel above, so d_u
 // is bit-identical and d_I differs only through the order of the float64 window adds.
-struct ShearGeom {
-    int nx, ny, nz;
-    int TX, TY, TZ;        // source tile
-    int WX, WY, WZ;        // window cells; x / y in virtual coordinates [-1, n], z inside the grid
-    int MX, MY, MZ;
-    int nseg;              // 16-cell z segments of the window
-    uint32_t ntx, nty, ntz, tiles_per_item, total, tile_vox, win_cells;
-    int rev;               // launch direction (common.hpp)
-    FastDiv d_tiles, d_tyz, d_tz, d_TyTz, d_Tz, d_wy;
-};
-
+// (ShearGeom, the placement, the window adds, the clamped atomics and the flush: splat_window.hpp)
 template <bool UNIT>
 __device__ __forceinline__ float shear_pos(int base, double dt, float u) {
     if (UNIT) return __builtin_fmaf((float)dt, u, (float)base);  // one rounding of the exact sum (common.hpp: sample_pos_t)
@@ -439,16 +404,8 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_num_sgpr(80))) void splat
     const uint32_t nv = (uint32_t)nx * ny * nz;
     const uint32_t planeB = nv * 4u;
 
-    // workgroup -> (batch item, tile)
-    const uint32_t L = block_order(blockIdx.x, sg.total, sg.rev);
-    const uint32_t n = sg.d_tiles.div(L);
-    uint32_t r = L - n * sg.tiles_per_item;
-    const uint32_t bx = sg.d_tyz.div(r);
-    r -= bx * (sg.nty * sg.ntz);
-    const uint32_t by = sg.d_tz.div(r);
-    const uint32_t bz = r - by * sg.ntz;
-    const int x0 = bx * sg.TX, y0 = by * sg.TY, z0 = bz * sg.TZ;
-    const int ex = min(sg.TX, nx - x0), ey = min(sg.TY, ny - y0), ez = min(sg.TZ, nz - z0);
+    const TileAt tl = tile_at(sg, nx, ny, nz);   // workgroup -> (batch item, tile)
+    const auto [n, x0, y0, z0, ex, ey, ez] = tl;
 
     const float *un = u + (size_t)n * 3 * nv;
     const float *In = BC ? I : I + (size_t)n * nc * nv;
@@ -458,25 +415,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_num_sgpr(80))) void splat
 
     const int WX = sg.WX, WY = sg.WY, WZ = sg.WZ;
     const int wez = min(WZ, nz);
-    // window z range: 16-aligned start (flush rows start on 64-byte boundaries), inside the grid
-    const int cxs = x0 + ex / 2, cys = y0 + ey / 2;
-    int wz0;
-    {
-        const float fdt = (float)dt;
-        const size_t sc = ((size_t)cxs * ny + cys) * nz + (z0 + ez / 2);
-        const int bzo = z0 + (int)floorf(fdt * un[sc + 2 * (size_t)nv]);
-        wz0 = max(0, min((bzo - sg.MZ) & ~15, nz - wez));
-    }
-    // origin of every z segment: the displacement of the tile's centre column at the segment's height
-    if ((int)threadIdx.x < sg.nseg) {
-        const float fdt = (float)dt;
-        const int zc = min(wz0 + (int)threadIdx.x * 16 + 8, nz - 1);
-        const size_t sc = ((size_t)cxs * ny + cys) * nz + zc;
-        int2 o;
-        o.x = max(-1, min(x0 + (int)floorf(fdt * un[sc]) - sg.MX, nx + 1 - WX));
-        o.y = max(-1, min(y0 + (int)floorf(fdt * un[sc + nv]) - sg.MY, ny + 1 - WY));
-        org[threadIdx.x] = o;
-    }
+    const int wz0 = shear_place(org, sg, tl, un, dt, wez);   // window z origin; (x, y) origin of every z segment
     const uint32_t sxB = (uint32_t)(WY * WZ) * 8u, syB = (uint32_t)WZ * 8u;            // window strides in bytes
     const uint32_t gxB = (uint32_t)ny * nz * 4u, gyB = (uint32_t)nz * 4u;              // grid strides in bytes
     const uint32_t wxu1 = (uint32_t)(WX - 1), wyu1 = (uint32_t)(WY - 1), wezu = (uint32_t)wez;
@@ -515,18 +454,8 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_num_sgpr(80))) void splat
             const int fx = lg_floor(hx), fy = lg_floor(hy), fz = lg_floor(hz);
             const float t = hx - (float)fx, uu = hy - (float)fy, v = hz - (float)fz;
             const float omt = 1.f - t, omu = 1.f - uu, omv = 1.f - v;
-            // sequentially flipped weights (include/interp.h:431-453): x outer, y, z inner
             float wq[8];
-            {
-                float ddx = omt, ddy = omu, ddz = omv;
-#pragma unroll
-                for (int q = 0; q < 8; ++q) {
-                    wq[q] = (ddx * ddy * ddz) * gv;
-                    ddz = 1.f - ddz;
-                    if (q & 1) ddy = 1.f - ddy;
-                    if ((q & 3) == 3) ddx = 1.f - ddx;
-                }
-            }
+            flipped_weights(wq, omt, omu, omv, gv);
             // the two z cells, clamped as the reference clamps them, and the window segment each falls in
             const int cz0 = clamp1(fz, nz), cz1 = clamp1(fz + 1, nz);
             const uint32_t lz0 = (uint32_t)(cz0 - wz0), lz1 = (uint32_t)(cz1 - wz0);
@@ -542,27 +471,13 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_num_sgpr(80))) void splat
             if (inwin) {
                 const uint32_t a0 = __umul24(lx0, sxB) + __umul24(ly0, syB) + lz0 * 8u;
                 const uint32_t a1 = __umul24(lx1, sxB) + __umul24(ly1, syB) + lz1 * 8u;
-                lds_add(reinterpret_cast<double *>(lago_smem + a0), (double)wq[0]);
-                lds_add(reinterpret_cast<double *>(lago_smem + a1), (double)wq[1]);
-                lds_add(reinterpret_cast<double *>(lago_smem + a0 + syB), (double)wq[2]);
-                lds_add(reinterpret_cast<double *>(lago_smem + a1 + syB), (double)wq[3]);
-                lds_add(reinterpret_cast<double *>(lago_smem + a0 + sxB), (double)wq[4]);
-                lds_add(reinterpret_cast<double *>(lago_smem + a1 + sxB), (double)wq[5]);
-                lds_add(reinterpret_cast<double *>(lago_smem + a0 + sxB + syB), (double)wq[6]);
-                lds_add(reinterpret_cast<double *>(lago_smem + a1 + sxB + syB), (double)wq[7]);
+                window_add8(lago_smem, a0, a1, sxB, syB, wq);
             } else {
                 // beyond the window: the reference's clamped global atomics (include/interp.h:330-401, :431-453)
                 const uint32_t X0 = __umul24((uint32_t)clamp1(fx, nx), gxB), X1 = __umul24((uint32_t)clamp1(fx + 1, nx), gxB);
                 const uint32_t Y0 = __umul24((uint32_t)clamp1(fy, ny), gyB), Y1 = __umul24((uint32_t)clamp1(fy + 1, ny), gyB);
                 const uint32_t Z0 = (uint32_t)cz0 * 4u, Z1 = (uint32_t)cz1 * 4u;
-                (void)__builtin_amdgcn_raw_ptr_buffer_atomic_fadd_f32(wq[0], rdI, X0 + Y0 + Z0, 0, 0);
-                (void)__builtin_amdgcn_raw_ptr_buffer_atomic_fadd_f32(wq[1], rdI, X0 + Y0 + Z1, 0, 0);
-                (void)__builtin_amdgcn_raw_ptr_buffer_atomic_fadd_f32(wq[2], rdI, X0 + Y1 + Z0, 0, 0);
-                (void)__builtin_amdgcn_raw_ptr_buffer_atomic_fadd_f32(wq[3], rdI, X0 + Y1 + Z1, 0, 0);
-                (void)__builtin_amdgcn_raw_ptr_buffer_atomic_fadd_f32(wq[4], rdI, X1 + Y0 + Z0, 0, 0);
-                (void)__builtin_amdgcn_raw_ptr_buffer_atomic_fadd_f32(wq[5], rdI, X1 + Y0 + Z1, 0, 0);
-                (void)__builtin_amdgcn_raw_ptr_buffer_atomic_fadd_f32(wq[6], rdI, X1 + Y1 + Z0, 0, 0);
-                (void)__builtin_amdgcn_raw_ptr_buffer_atomic_fadd_f32(wq[7], rdI, X1 + Y1 + Z1, 0, 0);
+                global_add8(rdI, X0, X1, Y0, Y1, Z0, Z1, wq);
             }
             if (NEED_U) {
                 float gx, gy, gz;
@@ -582,12 +497,9 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_num_sgpr(80))) void splat
                     buf_load2s(rI, o + dX, 0u, l1, h1);
                     buf_load2s(rI, o + dX + dY, 0u, l2, h2);
                     buf_load2s(rI, o + dY, 0u, l3, h3);
-                    const float c0 = f_hi ? h0 : l0, c1 = f_hi ? h1 : l1, c2 = f_hi ? h2 : l2, c3 = f_hi ? h3 : l3;
-                    const float c4 = c_lo ? l0 : h0, c5 = c_lo ? l1 : h1, c6 = c_lo ? l2 : h2, c7 = c_lo ? l3 : h3;
-                    // include/interp.h:315-326
-                    gx = lg_fma(omv, lg_fma(omu, c1 - c0, uu * (c2 - c3)), v * lg_fma(omu, c5 - c4, uu * (c6 - c7)));
-                    gy = lg_fma(omv, lg_fma(omt, c3 - c0, t * (c2 - c1)), v * lg_fma(omt, c7 - c4, t * (c6 - c5)));
-                    gz = lg_fma(omu, lg_fma(omt, c4 - c0, t * (c5 - c1)), uu * lg_fma(omt, c7 - c3, t * (c6 - c2)));
+                    const float cv[8] = {f_hi ? h0 : l0, f_hi ? h1 : l1, f_hi ? h2 : l2, f_hi ? h3 : l3,
+                                         c_lo ? l0 : h0, c_lo ? l1 : h1, c_lo ? l2 : h2, c_lo ? l3 : h3};
+                    lerp3_grad(cv, t, uu, v, gx, gy, gz);
                 }
                 // cuda/interp.cu:230: (Real)((double)diff * dt); for dt = +-1 that is +-diff exactly
                 const float diff = UNIT ? (float)dt * gv : (float)((double)gv * dt);
@@ -612,26 +524,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_num_sgpr(80))) void splat
             }
         }
         __syncthreads();
-        // flush touched cells: one wave per window row (lx, ly), lanes along z; the (x, y) a cell belongs to is
-        // its segment's origin + (lx, ly), folded onto the grid (the clamp of the reference)
-        {
-            const int lane = threadIdx.x & 63;
-            const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-            const uint32_t nrows = (uint32_t)(WX * WY);
-            for (uint32_t row = wave; row < nrows; row += NT / 64) {
-                const uint32_t lx = sg.d_wy.div(row), ly = row - lx * (uint32_t)WY;
-                const double *wrow = win + row * (uint32_t)WZ;
-                for (int lz = lane; lz < wez; lz += 64) {
-                    const double acc = wrow[lz];
-                    if (acc != 0.0) {
-                        const int2 o = org[lz >> 4];
-                        const uint32_t off = __umul24((uint32_t)clamp1(o.x + (int)lx, nx), gxB) +
-                                             __umul24((uint32_t)clamp1(o.y + (int)ly, ny), gyB) + (uint32_t)(wz0 + lz) * 4u;
-                        (void)__builtin_amdgcn_raw_ptr_buffer_atomic_fadd_f32((float)acc, rdI, off, 0, 0);
-                    }
-                }
-            }
-        }
+        shear_flush<NT, false>(win, org, sg, rdI, wez, wz0, gxB, gyB);   // touched cells
         __syncthreads();
     }
 }
@@ -662,16 +555,8 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_num_sgpr(80), amdgpu_wave
     const uint32_t planeB = nv * 4u;
     constexpr uint32_t NOWIN = 0xffffffffu, NOROW = 0xffffffffu, DEAD = 0xffffffffu;
 
-    // workgroup -> (batch item, tile)
-    const uint32_t L = block_order(blockIdx.x, sg.total, sg.rev);
-    const uint32_t n = sg.d_tiles.div(L);
-    uint32_t r = L - n * sg.tiles_per_item;
-    const uint32_t bx = sg.d_tyz.div(r);
-    r -= bx * (sg.nty * sg.ntz);
-    const uint32_t by = sg.d_tz.div(r);
-    const uint32_t bz = r - by * sg.ntz;
-    const int x0 = bx * sg.TX, y0 = by * sg.TY, z0 = bz * sg.TZ;
-    const int ex = min(sg.TX, nx - x0), ey = min(sg.TY, ny - y0), ez = min(sg.TZ, nz - z0);
+    const TileAt tl = tile_at(sg, nx, ny, nz);   // workgroup -> (batch item, tile)
+    const auto [n, x0, y0, z0, ex, ey, ez] = tl;
 
     const float *un = u + (size_t)n * 3 * nv;
     const float *In = BC ? I : I + (size_t)n * nc * nv;
@@ -681,23 +566,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_num_sgpr(80), amdgpu_wave
 
     const int WX = sg.WX, WY = sg.WY, WZ = sg.WZ;
     const int wez = min(WZ, nz);
-    const int cxs = x0 + ex / 2, cys = y0 + ey / 2;
-    int wz0;
-    {
-        const float fdt = (float)dt;
-        const size_t sc = ((size_t)cxs * ny + cys) * nz + (z0 + ez / 2);
-        const int bzo = z0 + (int)floorf(fdt * un[sc + 2 * (size_t)nv]);
-        wz0 = max(0, min((bzo - sg.MZ) & ~15, nz - wez));
-    }
-    if ((int)threadIdx.x < sg.nseg) {
-        const float fdt = (float)dt;
-        const int zc = min(wz0 + (int)threadIdx.x * 16 + 8, nz - 1);
-        const size_t sc = ((size_t)cxs * ny + cys) * nz + zc;
-        int2 o;
-        o.x = max(-1, min(x0 + (int)floorf(fdt * un[sc]) - sg.MX, nx + 1 - WX));
-        o.y = max(-1, min(y0 + (int)floorf(fdt * un[sc + nv]) - sg.MY, ny + 1 - WY));
-        org[threadIdx.x] = o;
-    }
+    const int wz0 = shear_place(org, sg, tl, un, dt, wez);   // window z origin; (x, y) origin of every z segment
     for (uint32_t f = threadIdx.x; f < sg.win_cells; f += NT) win[f] = 0.0;
     __syncthreads();
     const uint32_t sxB = (uint32_t)(WY * WZ) * 8u, syB = (uint32_t)WZ * 8u;            // window strides in bytes
@@ -806,28 +675,11 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_num_sgpr(80), amdgpu_wave
             const float gv = gvs[it];
             if (sv == DEAD) continue;
             const float omt = 1.f - FT[it], omu = 1.f - FU[it], omv = 1.f - FV[it];
-            // sequentially flipped weights (include/interp.h:431-453): x outer, y, z inner
             float wq[8];
-            {
-                float ddx = omt, ddy = omu, ddz = omv;
-#pragma unroll
-                for (int q = 0; q < 8; ++q) {
-                    wq[q] = (ddx * ddy * ddz) * gv;
-                    ddz = 1.f - ddz;
-                    if (q & 1) ddy = 1.f - ddy;
-                    if ((q & 3) == 3) ddx = 1.f - ddx;
-                }
-            }
+            flipped_weights(wq, omt, omu, omv, gv);
             const uint32_t a0 = A0[it], a1 = A1[it] & 0x3fffffffu;
             if (a0 != NOWIN) {
-                lds_add(reinterpret_cast<double *>(lago_smem + a0), (double)wq[0]);
-                lds_add(reinterpret_cast<double *>(lago_smem + a1), (double)wq[1]);
-                lds_add(reinterpret_cast<double *>(lago_smem + a0 + syB), (double)wq[2]);
-                lds_add(reinterpret_cast<double *>(lago_smem + a1 + syB), (double)wq[3]);
-                lds_add(reinterpret_cast<double *>(lago_smem + a0 + sxB), (double)wq[4]);
-                lds_add(reinterpret_cast<double *>(lago_smem + a1 + sxB), (double)wq[5]);
-                lds_add(reinterpret_cast<double *>(lago_smem + a0 + sxB + syB), (double)wq[6]);
-                lds_add(reinterpret_cast<double *>(lago_smem + a1 + sxB + syB), (double)wq[7]);
+                window_add8(lago_smem, a0, a1, sxB, syB, wq);
             } else {
                 // beyond the window: the reference's clamped global atomics (include/interp.h:330-401, :431-453)
                 uint32_t X0, X1, Y0, Y1, Z0, Z1;
@@ -838,14 +690,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_num_sgpr(80), amdgpu_wave
                     Z0 = (OG[it] & 1u) ? 4u : 0u;              // floor beyond the upper face: both cells are nz - 1 = zb + 1
                     Z1 = (OG[it] & 2u) ? 0u : 4u;              // floor below the lower face: both cells are 0 = zb
                 }
-                (void)__builtin_amdgcn_raw_ptr_buffer_atomic_fadd_f32(wq[0], rdI, X0 + Y0 + Z0, 0, 0);
-                (void)__builtin_amdgcn_raw_ptr_buffer_atomic_fadd_f32(wq[1], rdI, X0 + Y0 + Z1, 0, 0);
-                (void)__builtin_amdgcn_raw_ptr_buffer_atomic_fadd_f32(wq[2], rdI, X0 + Y1 + Z0, 0, 0);
-                (void)__builtin_amdgcn_raw_ptr_buffer_atomic_fadd_f32(wq[3], rdI, X0 + Y1 + Z1, 0, 0);
-                (void)__builtin_amdgcn_raw_ptr_buffer_atomic_fadd_f32(wq[4], rdI, X1 + Y0 + Z0, 0, 0);
-                (void)__builtin_amdgcn_raw_ptr_buffer_atomic_fadd_f32(wq[5], rdI, X1 + Y0 + Z1, 0, 0);
-                (void)__builtin_amdgcn_raw_ptr_buffer_atomic_fadd_f32(wq[6], rdI, X1 + Y1 + Z0, 0, 0);
-                (void)__builtin_amdgcn_raw_ptr_buffer_atomic_fadd_f32(wq[7], rdI, X1 + Y1 + Z1, 0, 0);
+                global_add8(rdI, X0, X1, Y0, Y1, Z0, Z1, wq);
             }
             const float t = FT[it], uu = FU[it], v = FV[it];
             float gx, gy, gz;
@@ -855,12 +700,9 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_num_sgpr(80), amdgpu_wave
                 auto hi = [](unsigned long long x) { return __builtin_bit_cast(float, (unsigned int)(x >> 32)); };
                 const float l0 = lo(pq[0]), l1 = lo(pq[1]), l2 = lo(pq[2]), l3 = lo(pq[3]);
                 const float h0 = hi(pq[0]), h1 = hi(pq[1]), h2 = hi(pq[2]), h3 = hi(pq[3]);
-                const float c0 = f_hi ? h0 : l0, c1 = f_hi ? h1 : l1, c2 = f_hi ? h2 : l2, c3 = f_hi ? h3 : l3;
-                const float c4 = c_lo ? l0 : h0, c5 = c_lo ? l1 : h1, c6 = c_lo ? l2 : h2, c7 = c_lo ? l3 : h3;
-                // include/interp.h:315-326
-                gx = lg_fma(omv, lg_fma(omu, c1 - c0, uu * (c2 - c3)), v * lg_fma(omu, c5 - c4, uu * (c6 - c7)));
-                gy = lg_fma(omv, lg_fma(omt, c3 - c0, t * (c2 - c1)), v * lg_fma(omt, c7 - c4, t * (c6 - c5)));
-                gz = lg_fma(omu, lg_fma(omt, c4 - c0, t * (c5 - c1)), uu * lg_fma(omt, c7 - c3, t * (c6 - c2)));
+                const float cv[8] = {f_hi ? h0 : l0, f_hi ? h1 : l1, f_hi ? h2 : l2, f_hi ? h3 : l3,
+                                     c_lo ? l0 : h0, c_lo ? l1 : h1, c_lo ? l2 : h2, c_lo ? l3 : h3};
+                lerp3_grad(cv, t, uu, v, gx, gy, gz);
             }
             // cuda/interp.cu:230: (Real)((double)diff * dt); for dt = +-1 that is +-diff exactly
             const float diff = UNIT ? (float)dt * gv : (float)((double)gv * dt);
@@ -875,26 +717,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_num_sgpr(80), amdgpu_wave
 #pragma unroll
         for (int it = 0; it < VPL; ++it) asm volatile("" : "+v"(pgv[it]));
         __syncthreads();
-        // flush touched cells (one wave per window row, lanes along z) and re-zero them for the next channel
-        {
-            const int lane = threadIdx.x & 63;
-            const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-            const uint32_t nrows = (uint32_t)(WX * WY);
-            for (uint32_t row = wave; row < nrows; row += NT / 64) {
-                const uint32_t lx = sg.d_wy.div(row), ly = row - lx * (uint32_t)WY;
-                double *wrow = win + row * (uint32_t)WZ;
-                for (int lz = lane; lz < wez; lz += 64) {
-                    const double acc = wrow[lz];
-                    if (acc != 0.0) {
-                        wrow[lz] = 0.0;
-                        const int2 o = org[lz >> 4];
-                        const uint32_t off = __umul24((uint32_t)clamp1(o.x + (int)lx, nx), gxB) +
-                                             __umul24((uint32_t)clamp1(o.y + (int)ly, ny), gyB) + (uint32_t)(wz0 + lz) * 4u;
-                        (void)__builtin_amdgcn_raw_ptr_buffer_atomic_fadd_f32((float)acc, rdI, off, 0, 0);
-                    }
-                }
-            }
-        }
+        shear_flush<NT, true>(win, org, sg, rdI, wez, wz0, gxB, gyB);   // touched cells, re-zeroed for the next channel
         __syncthreads();
     }
 #pragma unroll
@@ -911,6 +734,25 @@ static KnobArray<6> g_shear_cfg({8, 6, 0, 1, 1, 4});
 // g_shear_mc, several channels with d_u wanted: 0 d_u read-modify-written per channel, 1 d_u in registers over the
 // channels (splat_shear_kernel<..., VPL>), 2 (default) the geometry-once kernel (splat_shear_mc_kernel)
 static std::atomic<int> g_shear_nt{1024}, g_shear_on{1}, g_shear_mc{2};
+
+// The launch decomposition both geometries end in: tiles of TX x TY x TZ voxels over the source grid gs, nn batch items;
+// false when the tile count does not fit 31 bits.
+template <typename G>
+static bool fill_tile_grid(G &t, const Geom &gs, int TX, int TY, int TZ, int64_t nn, int rev) {
+    t.TX = TX; t.TY = TY; t.TZ = TZ;
+    t.ntx = (gs.nx + TX - 1) / TX;
+    t.nty = (gs.ny + TY - 1) / TY;
+    t.ntz = (gs.nz + TZ - 1) / TZ;
+    t.tiles_per_item = t.ntx * t.nty * t.ntz;
+    const int64_t total = (int64_t)t.tiles_per_item * nn;
+    if (total >= (1ll << 31)) return false;
+    t.total = (uint32_t)total;
+    t.rev = rev;
+    t.d_tiles = FastDiv(t.tiles_per_item);
+    t.d_tyz = FastDiv(t.nty * t.ntz);
+    t.d_tz = FastDiv(t.ntz);
+    return true;
+}
 
 // max_vox > 0 (the geometry-once multi-channel kernel): the tile is shrunk further, larger of TX / TY first, until it
 // has at most that many voxels.
@@ -949,26 +791,22 @@ static bool make_shear(ShearGeom &sg, const Geom &g, int64_t nn, size_t &smem, i
     }
     if ((uint64_t)sg.WY * sg.WZ * 8 >= (1u << 24) || (int64_t)TX * TY * TZ < 256) return false;
     sg.nx = g.nx; sg.ny = g.ny; sg.nz = g.nz;
-    sg.TX = TX; sg.TY = TY; sg.TZ = TZ;
     sg.MX = EX; sg.MY = EY; sg.MZ = EZ;
     sg.win_cells = (uint32_t)sg.WX * sg.WY * sg.WZ;
     smem = (size_t)sg.win_cells * sizeof(double) + (size_t)sg.nseg * 8;
-    sg.ntx = (g.nx + TX - 1) / TX;
-    sg.nty = (g.ny + TY - 1) / TY;
-    sg.ntz = (g.nz + TZ - 1) / TZ;
-    sg.tiles_per_item = sg.ntx * sg.nty * sg.ntz;
-    const int64_t total = (int64_t)sg.tiles_per_item * nn;
-    if (total >= (1ll << 31)) return false;
-    sg.total = (uint32_t)total;
-    sg.rev = g.rev;
+    if (!fill_tile_grid(sg, g, TX, TY, TZ, nn, g.rev)) return false;
     sg.tile_vox = (uint32_t)TX * TY * TZ;
-    sg.d_tiles = FastDiv(sg.tiles_per_item);
-    sg.d_tyz = FastDiv(sg.nty * sg.ntz);
-    sg.d_tz = FastDiv(sg.ntz);
     sg.d_TyTz = FastDiv((uint32_t)(TY * TZ));
     sg.d_Tz = FastDiv((uint32_t)TZ);
     sg.d_wy = FastDiv((uint32_t)sg.WY);
     return true;
+}
+
+// What follows the launch of an interp_backward splat: its error, or the path counter and the launch check.
+static int splat_launched(hipError_t e, hipStream_t s, int path, const char *what) {
+    if (e != hipSuccess) return fail_hip(e, what);
+    note_path(path);
+    return finish_launch(s, what);
 }
 
 // float32 displacement splat through the sheared-window kernel; returns 1 when the shape is left to the
@@ -991,9 +829,7 @@ static int interp_backward_shear(float *d_I, float *d_u, const float *go, const 
                            go, I, u, dt, nc, sg, umode, addgo);
             });
         }, unit_step, bc);
-        if (e != hipSuccess) return fail_hip(e, "interp_backward (sheared-window splat)");
-        note_path(LP_SPLAT_SHEAR_MC);
-        return finish_launch(s, "interp_backward (sheared-window splat)");
+        return splat_launched(e, s, LP_SPLAT_SHEAR_MC, "interp_backward (sheared-window splat)");
     }
     if (!make_shear(sg, g, nn, smem)) return 1;
     const int nt = shear_nt >= 1024 ? 1024 : (shear_nt >= 512 ? 512 : 256);
@@ -1010,9 +846,7 @@ static int interp_backward_shear(float *d_I, float *d_u, const float *go, const 
             });
         }, need_u, unit_step, bc);
     });
-    if (e != hipSuccess) return fail_hip(e, "interp_backward (sheared-window splat)");
-    note_path(LP_SPLAT_SHEAR);
-    return finish_launch(s, "interp_backward (sheared-window splat)");
+    return splat_launched(e, s, LP_SPLAT_SHEAR, "interp_backward (sheared-window splat)");
 }
 
 // g: target grid; gs: source grid (tiles): the same grid for interp / affine.  sc[d] = how many
@@ -1075,22 +909,11 @@ static bool make_tiles(TileGeom &tg, const Geom &g, const Geom &gs, int64_t nn, 
         else return false;
     }
     if ((int64_t)TX * TY * TZ < 256 && (int64_t)gs.nx * gs.ny * gs.nz >= 256) return false;  // not worth a window
-    tg.TX = TX; tg.TY = TY; tg.TZ = TZ;
     tg.win_cells = (uint32_t)tg.WX * tg.WY * tg.WZ;
     smem = (size_t)tg.win_cells * sizeof(double);
-    tg.ntx = (gs.nx + TX - 1) / TX;
-    tg.nty = (gs.ny + TY - 1) / TY;
-    tg.ntz = (gs.nz + TZ - 1) / TZ;
-    tg.tiles_per_item = tg.ntx * tg.nty * tg.ntz;
-    int64_t total = (int64_t)tg.tiles_per_item * nn;
-    if (total >= (1ll << 31)) return false;
-    tg.total = (uint32_t)total;
-    tg.rev = g.rev;
+    if (!fill_tile_grid(tg, gs, TX, TY, TZ, nn, g.rev)) return false;
     tg.tile_groups = (uint32_t)TX * TY * TZ;  // voxels per tile
     while (nthreads > 256 && (uint32_t)nthreads > tg.tile_groups) nthreads >>= 1;
-    tg.d_tiles = FastDiv(tg.tiles_per_item);
-    tg.d_tyz = FastDiv(tg.nty * tg.ntz);
-    tg.d_tz = FastDiv(tg.ntz);
     tg.d_TyTzq = FastDiv((uint32_t)(TY * TZ));
     tg.d_Tzq = FastDiv((uint32_t)TZ);
     tg.d_wey = FastDiv((uint32_t)(tg.WY < g.ny ? tg.WY : g.ny));
@@ -1147,17 +970,13 @@ int interp_backward_lds(R *d_I, R *d_u, const R *go, const R *I, const R *u, dou
             constexpr int MODE = UNIT() ? POS_DISP_UNIT : POS_DISP;
             return launch_tiled<R, MODE, BC(), true, V, true>(d_I, d_u, go, I, pa, nc, tg, smem, ntm, s);
         }, unit, bc);
-        if (e != hipSuccess) return fail_hip(e, "interp_backward (tiled splat)");
-        note_path(LP_SPLAT_TILED);
-        return finish_launch(s, "interp_backward (tiled splat)");
+        return splat_launched(e, s, LP_SPLAT_TILED, "interp_backward (tiled splat)");
     }
     const hipError_t e = with_flags([&](auto BC, auto NEED_U, auto VEC, auto UNIT) {
         constexpr int MODE = VEC() && UNIT() ? POS_DISP_UNIT : POS_DISP, VPL = VEC() ? V : 1;
         return launch_tiled<R, MODE, BC(), NEED_U(), VPL>(d_I, d_u, go, I, pa, nc, tg, smem, nt, s);
     }, bc, need_u, vec, unit);
-    if (e != hipSuccess) return fail_hip(e, "interp_backward (tiled splat)");
-    note_path(LP_SPLAT_TILED);
-    return finish_launch(s, "interp_backward (tiled splat)");
+    return splat_launched(e, s, LP_SPLAT_TILED, "interp_backward (tiled splat)");
 }
 
 // Image splat of affine_interp_backward (cuda/affine.cu:330-536, the d_I part), 3D.

@@ -58,7 +58,7 @@ def _tuned(ext, **fields):
         ext.tune(**saved)
 
 
-def _splat_sweep(ext, sp, dtype, want_path, needs=((True, True), (True, False)), ncs=(1, 3)):
+def _splat_sweep(ext, sp, dtype, want_path, needs=((True, True), (True, False)), ncs=(1, 3), dts=(1.0, -0.3)):
     """interp_backward over bc x (need_I, need_u) x dt x nc; want_path(nc, need_I, need_u) names the counter."""
     nn = 2
     rng = np.random.default_rng(hash(sp + (dtype == F64,)) % 2**31)
@@ -66,7 +66,7 @@ def _splat_sweep(ext, sp, dtype, want_path, needs=((True, True), (True, False)),
     for nc, bc in itertools.product(ncs, BOOLS):
         I = rnd(rng, ((1 if bc else nn), nc) + sp, dtype)
         go = rnd(rng, (nn, nc) + sp, dtype)
-        for (need_I, need_u), dt in itertools.product(needs, (1.0, -0.3)):
+        for (need_I, need_u), dt in itertools.product(needs, dts):
             what = f"{sp} nc={nc} bc={bc} need_I={need_I} need_u={need_u} dt={dt}"
             (dI, du), took = _took(ext, lambda: ext.interp_backward(dev(go), dev(I), dev(u), dt, need_I, need_u))
             assert took == {want_path(nc, need_I, need_u): 1}, (what, took)
@@ -80,6 +80,14 @@ def test_sheared_window_splat_arms(ext, sp):
     """need_u x unit x bc of splat_shear_kernel and unit x bc of splat_shear_mc_kernel, whose one-pass form serves the
     768-voxel tile and whose two-pass form the 1536-voxel one."""
     _splat_sweep(ext, sp, F32, lambda nc, need_I, need_u: "splat_shear_mc" if nc == 3 and need_u else "splat_shear")
+
+
+@pytest.mark.parametrize("sp", [(12, 10, 16), (20, 12, 40)])
+def test_geometry_once_splat_partial_tiles(ext, sp):
+    """splat_shear_mc_kernel (three channels, d_u wanted) on grids that are no multiple of the 8 x 6 x nz tile, so that the
+    shared tile decode, window placement and flush meet partial tiles in x and y: 768-voxel tiles in one pass at
+    (12, 10, 16); 1920-voxel tiles in two passes at (20, 12, 40), where the window's last z segment is half filled."""
+    _splat_sweep(ext, sp, F32, lambda nc, need_I, need_u: "splat_shear_mc", needs=((True, True),), ncs=(3,), dts=(1.0, -0.2))
 
 
 @pytest.mark.parametrize("nthreads", [1024, 512, 256])
