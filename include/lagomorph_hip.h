@@ -44,6 +44,12 @@ extern "C" {
 #define LAGO_GAUSS_WRAP 0
 #define LAGO_GAUSS_ZERO 1
 
+/* lago_mi_histogram / lago_mi_backward: the bin counts B a table side takes, and the fraction bits of the fixed-point
+ * histogram (one voxel's whole weight is 2^LAGO_MI_FRAC_BITS) */
+#define LAGO_MI_MIN_BINS 4
+#define LAGO_MI_MAX_BINS 64
+#define LAGO_MI_FRAC_BITS 32
+
 /* ---- housekeeping --------------------------------------------------------- */
 
 /* replaces set_debug_mode (extension.cpp:105-107): when non-zero every entry
@@ -331,10 +337,50 @@ long long lago_reversed_launches(void);
      * J's fields and the shared G[g cX]).  Pointwise, in double, rounded once; an output may not overlap an input  \
      * or the other output.  No counterpart in the reference. */                                                    \
     int lago_lncc_combine##SUF(REAL *dI, REAL *dJ, const REAL *smoothed, const REAL *I, const REAL *J, int which,   \
-                               int64_t n, void *stream);
+                               int64_t n, void *stream);                                                            \
+    /* mutual information (no counterpart in the reference): the Parzen-window joint histogram of two fields I, J   \
+     * of `rows` = N*C scalar fields of extent (nx, ny[, nz]), one bins x bins table P per row, bins = B in         \
+     * LAGO_MI_MIN_BINS..LAGO_MI_MAX_BINS.  Each image has a range (lo, hi), lo < hi, both finite, passed by value  \
+     * (the call may be captured in a graph).  Per voxel, in double for both precisions and in this order (nothing  \
+     * is fused):                                                                                                   \
+     *       s = (B - 3) / (hi - lo)    vc = fmin(fmax(v, lo), hi)   (a NaN voxel counts as lo)                      \
+     *       c = (vc - lo) * s + 1      k = min(floor(c), B - 3) - 1, clamped as an integer to [0, B - 4]            \
+     *       t = c - (k + 1), u = 1 - t                                                                             \
+     *       w0 = u u u / 6   w1 = ((3 t - 6) t t + 4) / 6   w2 = (((-3 t + 3) t + 3) t + 1) / 6   w3 = t t t / 6      \
+     * (cubic B-spline windows on both images: a voxel touches bins kI..kI+3 x kJ..kJ+3), and                       \
+     *       H[kI + a][kJ + b] += llrint(wI_a * wJ_b * 2^32)   as a signed 64-bit integer sum                       \
+     *       P = H / ((double)nvox * 2^32)                     nvox the voxels of one row, 2^30 at most             \
+     * The integer sum is associative: P has the same bits from call to call, on any stream and for any number of   \
+     * scratch tables, and equals a sequential evaluation integer for integer.  scratch: `scratch_tables` >= 1      \
+     * tables of bins x bins 64-bit integers PER ROW, (rows, scratch_tables, B, B), clobbered (workgroups write      \
+     * partial tables there with plain stores and a second kernel sums them: no memset, no global atomic);          \
+     * lago_mi_scratch_tables says how many the call can use, fewer only cost speed.  P and scratch may not overlap \
+     * an input or each other; I may equal J.  LAGO_ERR_INVALID: bins out of range, lo >= hi or a bound that is not \
+     * finite (or a range so wide or narrow that s is not), more than 2^30 voxels in a row, dim not 2 or 3.         \
+     * rows == 0 or an extent of 0: nothing is done (LAGO_OK).  No counterpart in the reference. */                 \
+    int lago_mi_histogram##SUF(double *P, const REAL *I, const REAL *J, long long *scratch, int64_t scratch_tables, \
+                               int bins, double loI, double hiI, double loJ, double hiJ, int dim, int64_t rows,     \
+                               int64_t nx, int64_t ny, int64_t nz, void *stream);                                   \
+    /* lago_mi_backward: for G = dL/dP (rows, B, B) and the windows' derivatives                                    \
+     *       w0' = -(u u) / 2 s   w1' = (3 t - 4) t / 2 s   w2' = ((-3 t + 2) t + 1) / 2 s   w3' = t t / 2 s         \
+     * (all four 0 unless lo <= v <= hi: 0 for NaN, +-inf and clamped voxels)                                       \
+     *       dI(x) = (sum_a wI_a'(I(x)) (sum_b wJ_b(J(x)) G[kI + a][kJ + b])) / nvox        a, b ascending          \
+     *       dJ(x) = (sum_b wJ_b'(J(x)) (sum_a wI_a(I(x)) G[kI + a][kJ + b])) / nvox                                \
+     * in double, rounded once to REAL: the gradient of the unquantised histogram.  The two are one function with   \
+     * the roles swapped and G transposed, bit for bit.  dI or dJ may be NULL: that gradient is neither computed    \
+     * nor written.  A pure gather: the same bits from call to call.  An output may not overlap an input or the     \
+     * other output.  Errors and empty extents as for lago_mi_histogram.  No counterpart in the reference. */       \
+    int lago_mi_backward##SUF(REAL *dI, REAL *dJ, const double *G, const REAL *I, const REAL *J, int bins,          \
+                              double loI, double hiI, double loJ, double hiJ, int dim, int64_t rows, int64_t nx,    \
+                              int64_t ny, int64_t nz, void *stream);
 
 LAGO_DECLARE(float, _f32)
 LAGO_DECLARE(double, _f64)
+
+/* How many scratch tables per row lago_mi_histogram can use for `rows` rows of `nvox` voxels at `bins` bins (>= 1: a
+ * row is cut into chunks of a few thousand voxels, as many as keep the scratch of all rows within 8 MB).  The caller
+ * allocates rows x this x bins x bins 64-bit integers.  No counterpart in the reference. */
+int lago_mi_scratch_tables(int bins, int64_t rows, int64_t nvox);
 
 /* ---- fused geometry operators (beyond the reference's extension surface) -------------
  * compose: out = ds*u + dt*interp(v, u, ds) in one pass -- deform.compose

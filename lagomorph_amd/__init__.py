@@ -22,7 +22,8 @@ if not _BUILDING:
     from .lagomorph_ext import set_debug_mode  # noqa: F401
     from .lddmm import EPDiff_step, LDDMMAtlasBuilder, expmap, expmap_advect, lddmm_step, shard_indices  # noqa: F401
     from .metric import FluidMetric, FluidMetricOperator, GaussianMetric, Metric  # noqa: F401
-    from .similarity import LNCCFunction, LNCCSimilarity, lncc, lncc_loss  # noqa: F401
+    from .similarity import (JointHistogramFunction, LNCCFunction, LNCCSimilarity, MISimilarity,  # noqa: F401
+                             joint_histogram, lncc, lncc_loss, mi_loss, mutual_information)
     from .smooth import GaussianSmoothFunction, gaussian_smooth, gaussian_taps  # noqa: F401
 
     __version__ = "0.1.0"

@@ -78,6 +78,8 @@ _SIGS = {
     "lago_lncc_cc": [_vp, _vp, _dbl, _i64, _vp],
     "lago_lncc_coeffs": [_vp, _vp, _vp, _dbl, _int, _i64, _vp],
     "lago_lncc_combine": [_vp, _vp, _vp, _vp, _vp, _int, _i64, _vp],
+    "lago_mi_histogram": [_vp, _vp, _vp, _vp, _i64, _int, _dbl, _dbl, _dbl, _dbl, _int, _i64, _i64, _i64, _i64, _vp],
+    "lago_mi_backward": [_vp, _vp, _vp, _vp, _vp, _int, _dbl, _dbl, _dbl, _dbl, _int, _i64, _i64, _i64, _i64, _vp],
     "lago_fluid_metric": [_vp, _vp, _vp, _i64, _int, _vp, _vp, _vp, _vp, _vp, _vp, _dbl, _dbl, _dbl, _int, _i64, _i64,
                           _i64, _i64, _vp],
     "lago_fluid_metric_scaled": [_vp, _vp, _vp, _i64, _int, _vp, _vp, _vp, _vp, _vp, _vp, _dbl, _dbl, _dbl, _int, _i64,
@@ -93,6 +95,8 @@ for _name, _args in _SIGS.items():
         _f.restype = _int
         _fn[_name + _suf] = _f
 _lib.lago_set_debug.argtypes = [_int]
+_lib.lago_mi_scratch_tables.argtypes = [_int, _i64, _i64]
+_lib.lago_mi_scratch_tables.restype = _int
 
 
 class LagoTuning(ctypes.Structure):
@@ -676,6 +680,72 @@ def lncc_backward(grad_out, I, J, moments, radii, taps, mode, eps, need_I=True, 
     d_I = torch.empty_like(I) if need_I else None
     d_J = torch.empty_like(J) if need_J else None
     _call("lago_lncc_combine", I, _ptr(d_I), _ptr(d_J), _ptr(sm), _ptr(I), _ptr(J), which, n)
+    return d_I, d_J
+
+
+MI_MIN_BINS, MI_MAX_BINS, MI_FRAC_BITS = 4, 64, 32   # LAGO_MI_* of include/lagomorph_hip.h
+
+
+def _check_mi(I, J, bins, range_I, range_J):
+    """The checks mi_histogram and mi_backward share: (dim, nx, ny, nz, bins, (loI, hiI), (loJ, hiJ))."""
+    _check_input(I, "I")
+    _check_input(J, "J")
+    _suffix(I)
+    _same(I, J)
+    dim, nx, ny, nz = _spatial(I)
+    if dim not in (2, 3):
+        raise RuntimeError("Only two- and three-dimensional mutual information is supported")
+    if J.shape != I.shape:
+        raise RuntimeError(f"mutual_information: I {tuple(I.shape)} and J {tuple(J.shape)} must have the same shape")
+    return (dim, nx, ny, nz, mi_bins(bins), mi_range(range_I, "range_I"), mi_range(range_J, "range_J"))
+
+
+def mi_bins(bins):
+    if isinstance(bins, bool) or int(bins) != bins or not MI_MIN_BINS <= int(bins) <= MI_MAX_BINS:
+        raise ValueError(f"mutual_information: bins must be an integer in {MI_MIN_BINS}..{MI_MAX_BINS} (got {bins!r})")
+    return int(bins)
+
+
+def mi_range(r, name):
+    """(lo, hi) as floats; ValueError unless both are finite and lo < hi."""
+    try:
+        lo, hi = (float(v) for v in r)
+    except (TypeError, ValueError):
+        raise ValueError(f"mutual_information: {name} must be a pair (lo, hi) of numbers (got {r!r})") from None
+    if not (math.isfinite(lo) and math.isfinite(hi) and lo < hi):
+        raise ValueError(f"mutual_information: {name} needs finite bounds lo < hi (got ({lo}, {hi}))")
+    return lo, hi
+
+
+def mi_histogram(I, J, bins, range_I, range_J):
+    """The Parzen-window joint histogram P (N, C, bins, bins), float64, of I and J (N, C, *sp) over the ranges
+    (lo, hi) of the two images: cubic B-spline windows on both, summed as 64-bit fixed-point integers, so that P has
+    the same bits from call to call (csrc/mi.hip: mi_hist_kernel, mi_reduce_kernel; the definition is in
+    include/lagomorph_hip.h).  The scratch of partial tables is allocated here.  Not in the reference; no CPU path."""
+    dim, nx, ny, nz, bins, (loI, hiI), (loJ, hiJ) = _check_mi(I, J, bins, range_I, range_J)
+    rows, nvox = I.size(0) * I.size(1), nx * ny * nz
+    P = torch.empty((I.size(0), I.size(1), bins, bins), dtype=torch.float64, device=I.device)
+    tables = int(_lib.lago_mi_scratch_tables(bins, rows, nvox))
+    scratch = torch.empty((rows * tables * bins * bins,), dtype=torch.int64, device=I.device)
+    _call("lago_mi_histogram", I, _ptr(P), _ptr(I), _ptr(J), _ptr(scratch), tables, bins, loI, hiI, loJ, hiJ, dim, rows,
+          nx, ny, nz)
+    return P
+
+
+def mi_backward(G, I, J, bins, range_I, range_J, need_I=True, need_J=True):
+    """(dI, dJ) of mi_histogram for the upstream gradient G = dL/dP (N, C, bins, bins), float64: one gather pass from
+    the row's table in LDS (csrc/mi.hip: mi_bwd_kernel).  A gradient that is not needed is None, neither computed nor
+    written.  Not in the reference; no CPU path."""
+    dim, nx, ny, nz, bins, (loI, hiI), (loJ, hiJ) = _check_mi(I, J, bins, range_I, range_J)
+    _check_input(G, "G")
+    if G.dtype != torch.float64 or G.device != I.device or tuple(G.shape) != (I.size(0), I.size(1), bins, bins):
+        raise RuntimeError("mi_backward: G must be a float64 tensor (N, C, bins, bins) on the device of I")
+    if not (need_I or need_J):
+        return None, None
+    d_I = torch.empty_like(I) if need_I else None
+    d_J = torch.empty_like(J) if need_J else None
+    _call("lago_mi_backward", I, _ptr(d_I), _ptr(d_J), _ptr(G), _ptr(I), _ptr(J), bins, loI, hiI, loJ, hiJ, dim,
+          I.size(0) * I.size(1), nx, ny, nz)
     return d_I, d_J
 
 
