@@ -142,6 +142,10 @@ typedef struct lago_tuning {
      * invertible with a moderate inverse (decided per item on the device), the general tiled LDS splat for the others;
      * 0: the general tiled splat for every item.  d_I differs by the order of its sums */
     int32_t affine_box;
+    /* 1 (default): a compose called with the near-identity hint (lago_compose_near_*) and eligible for the LDS window takes
+     * the fixed-origin form with two windows in flight (csrc/fused.hip: compose3_near_kernel); 0: the hint is ignored.
+     * Same bits */
+    int32_t compose_near;
 } lago_tuning;
 /* the settings in force / the library's defaults: fills t->struct_size bytes (struct_size set by the caller) */
 void lago_get_tuning(lago_tuning *t);
@@ -165,6 +169,7 @@ int lago_set_tuning(const lago_tuning *t);
 #define LAGO_PATH_SPLAT_2D 11      /* LDS-privatised 2D splat (interp_backward of 2D fields) */
 #define LAGO_PATH_SPLAT_AFFINE_BOX 12 /* affine_interp_backward's image splat by target boxes */
 #define LAGO_PATH_FLUID_GENERIC 13 /* lago_fluid_metric: generic hand-written FFT passes (any extent, both precisions) */
+#define LAGO_PATH_GATHER_WINDOW_NEAR 14 /* compose with the near-identity hint: fixed-origin LDS windows, two in flight */
 long long lago_path_launches(int path);
 /* Launch direction (lago_tuning.launch_order): launches so far that walked their workgroups in DESCENDING order.  Kernels
  * whose results do not depend on the block order alternate (a consumer starts on what the Infinity Cache still holds of
@@ -391,6 +396,15 @@ int lago_compose_f32(float *out, const float *u, const float *v, double ds, doub
                      int64_t nx, int64_t ny, int64_t nz, void *stream);
 int lago_compose_f64(double *out, const double *u, const double *v, double ds, double dt, int dim, int64_t nn,
                      int64_t nx, int64_t ny, int64_t nz, void *stream);
+/* The same with a hint: the caller expects |ds u| below one voxel everywhere, as in the Euler step of a shoot
+ * (phi <- phi o (id - dt v)).  The hint changes speed only, never values: float32 3D calls that qualify for the LDS
+ * window take a form whose window sits on the tile itself (lago_tuning.compose_near; LAGO_PATH_GATHER_WINDOW_NEAR), and
+ * samples or whole tiles that are farther away than promised are served as lago_compose serves them.  Every other call
+ * is lago_compose. */
+int lago_compose_near_f32(float *out, const float *u, const float *v, double ds, double dt, int dim, int64_t nn,
+                          int64_t nx, int64_t ny, int64_t nz, void *stream);
+int lago_compose_near_f64(double *out, const double *u, const double *v, double ds, double dt, int dim, int64_t nn,
+                          int64_t nx, int64_t ny, int64_t nz, void *stream);
 
 /* lincomb: out[i] = c0 x0[i] + c1 x1[i] + ... (k = 1..4 terms, n elements), evaluated left to right with one fma per
  * term in the tensors' precision -- the elementwise sums of lddmm_step (lddmm.py:300-325: the regulariser's gradient

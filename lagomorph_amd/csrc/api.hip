@@ -65,6 +65,7 @@ static lago_tuning default_tuning() {
     t.fluid_xpass_wide = 1;
     t.fluid_xpass_persist = 1;
     t.affine_box = 1;
+    t.compose_near = 1;
     return t;
 }
 static lago_tuning g_tuning = default_tuning();
@@ -97,7 +98,7 @@ int lago_set_tuning(const lago_tuning *t) {
     lago::g_interp_vec = g.vector_kernels ? 1 : 0;
     lago::g_launch_alt = g.launch_order ? 1 : 0;
     lago::tune_splat(g.splat_tile, g.splat_shear, g.splat_shear_mc, g.splat_mc);
-    lago::tune_fused(g.stencil_tile, g.gather_window);
+    lago::tune_fused(g.stencil_tile, g.gather_window, g.compose_near);
     lago::tune_fluid(g.fluid_mode);
     lago::tune_fluid_passes(g.fluid_xpass_ipw, g.fluid_zy_persist, g.fluid_xpass_wide, g.fluid_xpass_persist);
     lago::tune_affine(g.affine_box);

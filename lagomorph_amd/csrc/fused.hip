@@ -206,11 +206,130 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(4, 4))) void
         channels(std::false_type{});
 }
 
+// Near-identity form, for the Euler step of a shoot (compose(v, phi, -dt, 1): |ds u| below one voxel).  The window
+// (GWNear, gather_window.hpp) sits on the tile itself, so nothing has to be loaded before it can be moved, and it is
+// small enough for two per workgroup: channels 0 and 1 are on their way at kernel entry (A, B), channel 2 follows into A
+// as soon as channel 0 has been read, and flies while channel 1 is read from B.  One dependent round trip (u, beside the
+// windows) and three barriers instead of four round trips and five barriers.  The caller's hint picks this kernel
+// (lago_compose_near); a wrong hint costs time, not bits: samples outside the small window are strays as above.  (A
+// workgroup-uniform fallback to the translated window inside this kernel, or one body shared with
+// compose3_window_kernel through a function, both spill at the 128 VGPRs of this occupancy -- 5 to 30 registers, in
+// either kernel -- so the two kernels stand side by side and a far-off tile is served by strays alone.)
+// Same value expression, roundings, clamping and stray path as compose3_window_kernel: same bits.
+template <int NT, int U, bool UNIT>
+__global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(4, 4))) void compose3_near_kernel(
+    float *__restrict__ out, const float *__restrict__ u, const float *__restrict__ v, double ds, double dt, Geom g, GWGrid w) {
+    using G = GWNear;
+    extern __shared__ float gwin[];  // A: gwin, B: gwin + kWin
+    constexpr int XS = NT / (32 * G::TY), kWin = G::NCHUNK * 4;
+    static_assert(XS * U == G::TX && NT % (32 * G::TY) == 0, "tile shape");
+    const GWTile tl = gw_tile(w, g.rev);
+    const size_t nv = g.nvox;
+    const uint32_t plane = g.nvox * 4u;
+    const float *un = u + (size_t)tl.n * 3 * nv;
+    const float *vn = v + (size_t)tl.n * 3 * nv;
+    float *on = out + (size_t)tl.n * 3 * nv;
+    const float dsr = (float)ds, dtr = (float)dt;
+    const int lz = threadIdx.x & 31, ly = (threadIdx.x >> 5) & (G::TY - 1), lxb = threadIdx.x / (32 * G::TY);
+    const int j = tl.y0 + ly, k = tl.z0 + lz;
+
+    // the origin is the tile's own: channels 0 and 1 are moving before anything else is loaded
+    const GWOrigin o = gw_origin_near(tl);
+    GWLoader<NT, G> ld;
+    ld.plan(o, g);
+    ld.issue(vn, plane, gwin);
+    ld.issue(vn + nv, plane, gwin + kWin);
+
+    const bool row_ok = j < g.ny && k < g.nz;
+    const uint32_t off0 = (((uint32_t)(tl.x0 + lxb) * (uint32_t)g.ny + (uint32_t)j) * (uint32_t)g.nz + (uint32_t)k) * 4u;
+    const uint32_t estep = (uint32_t)XS * (uint32_t)g.ny * (uint32_t)g.nz * 4u;
+    auto voff = [&](int e) { return row_ok && tl.x0 + lxb + XS * e < g.nx ? off0 + (uint32_t)e * estep : G::kOutside; };
+    GWLerpT<G> L[U];
+    uint32_t outm = 0;  // bit e: sample e has a corner outside the window
+    float uu[3][U];
+    {
+#pragma unroll
+        for (int e = 0; e < U; ++e) {
+#pragma unroll
+            for (int d = 0; d < 3; ++d)
+                uu[d][e] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(make_rsrc(un + (size_t)d * nv, plane), voff(e), 0, LAGO_COMPOSE_AUX_LD));
+        }
+#pragma unroll
+        for (int e = 0; e < U; ++e) {
+            const int i = tl.x0 + lxb + XS * e;
+            const bool in = L[e].setup(sample_pos_t<float, UNIT>(i, ds, uu[0][e]), sample_pos_t<float, UNIT>(j, ds, uu[1][e]),
+                                       sample_pos_t<float, UNIT>(k, ds, uu[2][e]), g, o);
+            outm |= (in | (voff(e) == G::kOutside)) ? 0u : 1u << e;
+            __builtin_amdgcn_sched_barrier(0);  // one sample at a time, as in compose3_window_kernel
+        }
+    }
+    auto channels = [&](auto stray) {
+        constexpr bool STRAY = decltype(stray)::value;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            const float *win = c == 1 ? gwin + kWin : gwin;  // (B needs no wait: it landed before the first barrier)
+            if (c == 2) {
+                // Covers the loads of channel 2's window (-> A), issued below behind the barrier that freed A.  Vector
+                // memory operations retire in issue order, and channel 1's U stores were issued after those loads: with
+                // at most U operations outstanding the loads are among the retired.  (The pair gathers of strays come
+                // after them as well and only raise the number issued since.)  Not vmcnt(0): the stores need not have
+                // reached memory.  A bare barrier: __syncthreads() would bring that vmcnt(0) with it.
+                static_assert(U == 8, "the count below");
+                asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
+                __builtin_amdgcn_s_barrier();
+                asm volatile("" ::: "memory");
+            }
+            const BufRsrc ro = make_rsrc(on + (size_t)c * nv, plane);
+#pragma unroll
+            for (int e = 0; e < U; ++e) {
+                float val = L[e].value(win);
+                if constexpr (STRAY) {
+                    const bool mine = outm & (1u << e);
+                    if (__builtin_amdgcn_ballot_w64(mine) != 0) {  // wave-uniform
+                        if (mine) {
+                            const int i = tl.x0 + lxb + XS * e;
+                            Lerp3<float, false> P;
+                            P.setup(sample_pos_t<float, UNIT>(i, ds, uu[0][e]), sample_pos_t<float, UNIT>(j, ds, uu[1][e]),
+                                    sample_pos_t<float, UNIT>(k, ds, uu[2][e]), g.nx, g.ny, g.nz);
+                            val = P.value(vn + (size_t)c * nv);
+                        }
+                    }
+                }
+                const float a = dsr * uu[c][e];
+                const float b = dtr * val;
+                __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(uint32_t, a + b), ro, voff(e), 0, LAGO_COMPOSE_AUX_ST);
+            }
+            if (c == 0) {
+                // Covers this wave's LDS reads of channel 0 (their values are in the stores above, so the count is zero
+                // already); behind the barrier everyone has read A, and channel 2's window goes into it while channel 1
+                // is read from B.
+                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+                __builtin_amdgcn_s_barrier();
+                asm volatile("" ::: "memory");
+                ld.issue(vn + (size_t)2 * nv, plane, gwin);
+                asm volatile("" ::: "memory");
+                __builtin_amdgcn_sched_barrier(0);  // channel 1's stores stay behind these loads: the count at c == 2
+            }
+        }
+    };
+    // Covers the loads of both windows: they were issued before the u loads, whose values the setups above have consumed,
+    // so nothing is outstanding here any more (a count that waited for A alone would be 4 + 24, and is passed long before).
+    // Behind this barrier A and B have landed for every wave.
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    if (__syncthreads_or(outm != 0))
+        channels(std::true_type{});
+    else
+        channels(std::false_type{});
+}
+
 // (explicit instantiations: hipcc 7.2 drops the host stub of a variant that is only named in the `else` of a launch)
 template __global__ void compose3_window_kernel<GW::NT, 8, true>(float *, const float *, const float *, double, double, Geom, GWGrid);
 template __global__ void compose3_window_kernel<GW::NT, 8, false>(float *, const float *, const float *, double, double, Geom, GWGrid);
+template __global__ void compose3_near_kernel<GW::NT, 8, true>(float *, const float *, const float *, double, double, Geom, GWGrid);
+template __global__ void compose3_near_kernel<GW::NT, 8, false>(float *, const float *, const float *, double, double, Geom, GWGrid);
 
 std::atomic<int> g_gather_window{1};  // 1: LDS-window gathers where the shape allows (default); 0: pair gathers only
+std::atomic<int> g_compose_near{1};   // 1 (default): a compose called with the near-identity hint takes compose3_near_kernel; 0: the hint is ignored
 std::atomic<int> g_tile_cube{1};      // 1: 128^3 / 160^3 volumes take the instantiations with compile-time geometry
 
 // Profiling builds only (-DLAGO_PROFILING; round 4, VERDICT r3 item 2, tools/ab_streams.py): LAGO_EXP_GATHER_PAD=<bytes>
@@ -232,7 +351,7 @@ static size_t padded_smem(size_t smem) {
 // returns kNotTaken when the shape is left to the other kernels
 template <typename R>
 static int compose_window_launch(R *out, const R *u, const R *v, double ds, double dt, const Geom &g, int64_t nn,
-                                 hipStream_t s) {
+                                 hipStream_t s, bool near) {
     if constexpr (sizeof(R) == 4) {
         GWGrid w;
         if (!make_gwgrid(w, g, nn) || ((uintptr_t)v & 15u)) return kNotTaken;
@@ -240,11 +359,14 @@ static int compose_window_launch(R *out, const R *u, const R *v, double ds, doub
         // (compiling the geometry of 128^3 / 160^3 volumes in, as ad_star3_tile_kernel does, costs this kernel 2-15
         // spilled registers at its 128: not done)
         const hipError_t e = with_flags([&](auto UNIT) {
+            if (near)
+                return launch(compose3_near_kernel<NT, U, UNIT()>, dim3(w.total), dim3(NT),
+                              padded_smem(2 * GWNear::lds_bytes<NT>()), s, out, u, v, ds, dt, g, w);
             return launch(compose3_window_kernel<NT, U, UNIT()>, dim3(w.total), dim3(NT), padded_smem(GW::lds_bytes<NT>()), s,
                           out, u, v, ds, dt, g, w);
         }, unit_dt<R>(ds));
         if (e != hipSuccess) return fail_hip(e, "compose");
-        note_path(LP_GATHER_WINDOW);
+        note_path(near ? LP_GATHER_WINDOW_NEAR : LP_GATHER_WINDOW);
         return LAGO_OK;
     }
     return kNotTaken;
@@ -252,7 +374,7 @@ static int compose_window_launch(R *out, const R *u, const R *v, double ds, doub
 
 template <typename R>
 static int compose_impl(R *out, const R *u, const R *v, double ds, double dt, int dim, int64_t nn, int64_t nx,
-                        int64_t ny, int64_t nz, void *stream) {
+                        int64_t ny, int64_t nz, void *stream, bool near = false) {
     if (dim != 2 && dim != 3) return fail_invalid("Only two- and three-dimensional interpolation is supported");
     Geom g;
     if (!make_geom(g, dim, nn, nx, ny, nz)) return fail_invalid("compose: bad extent");
@@ -261,7 +383,7 @@ static int compose_impl(R *out, const R *u, const R *v, double ds, double dt, in
     hipStream_t s = (hipStream_t)stream;
     constexpr int U = 2;
     if (dim == 3 && g_interp_vec && g_gather_window && g.nvox >= 32768u) {
-        const int rc = compose_window_launch(out, u, v, ds, dt, g, nn, s);
+        const int rc = compose_window_launch(out, u, v, ds, dt, g, nn, s, near && g_compose_near);
         if (rc != kNotTaken) return rc != LAGO_OK ? rc : finish_launch(s, "compose");
     }
     uint32_t nbx_u, nb;
@@ -638,7 +760,8 @@ int lincomb_impl(R *out, int k, const R *x0, const R *x1, const R *x2, const R *
 }  // namespace lago
 
 namespace lago {
-void tune_fused(int stencil_tile, int gather_window) {
+void tune_fused(int stencil_tile, int gather_window, int compose_near) {
+    g_compose_near = compose_near ? 1 : 0;
     // stencil_tile 0: direct kernels; 1: row tiles (default); 3: row tiles without the compile-time-geometry instantiations
     g_stencil_tile = stencil_tile ? 1 : 0;
     g_tile_cube = stencil_tile == 3 ? 0 : 1;
@@ -662,6 +785,14 @@ int lago_compose_f32(float *out, const float *u, const float *v, double ds, doub
 int lago_compose_f64(double *out, const double *u, const double *v, double ds, double dt, int dim, int64_t nn,
                      int64_t nx, int64_t ny, int64_t nz, void *stream) {
     return lago::compose_impl<double>(out, u, v, ds, dt, dim, nn, nx, ny, nz, stream);
+}
+int lago_compose_near_f32(float *out, const float *u, const float *v, double ds, double dt, int dim, int64_t nn,
+                          int64_t nx, int64_t ny, int64_t nz, void *stream) {
+    return lago::compose_impl<float>(out, u, v, ds, dt, dim, nn, nx, ny, nz, stream, true);
+}
+int lago_compose_near_f64(double *out, const double *u, const double *v, double ds, double dt, int dim, int64_t nn,
+                          int64_t nx, int64_t ny, int64_t nz, void *stream) {
+    return lago::compose_impl<double>(out, u, v, ds, dt, dim, nn, nx, ny, nz, stream, true);
 }
 int lago_Ad_star_f32(float *out, float *mphi, const float *phiinv, const float *m, int dim, int64_t nn, int64_t nx,
                      int64_t ny, int64_t nz, void *stream) {

@@ -11,29 +11,41 @@
 // pair the pair-gather uses, same selects, same value expression -> bit-identical results).
 //
 // Geometry: a workgroup of NT = 512*XS threads owns TX x TY x TZ = 8 x 16 x 32 voxels (lane = z, 16 rows
-// of y, XS x-slabs, U = 8/XS voxels per lane along x).  The window is WX x WY = 13 x 21 rows of WZ = 44
-// floats (11 chunks), i.e. the tile plus a halo of 2 voxels in x / y and at least 4 in z around the
-// position the tile's centre voxel is displaced to.  One channel's window is 48 KB: two workgroups per CU.
+// of y, XS x-slabs, U = 8/XS voxels per lane along x).  Two windows (GWGeom<H, HZ, WZC>), WX x WY = (TX + 1 + 2 H) x
+// (TY + 1 + 2 H) rows of WZ = 4 WZC floats each:
+//   GW      H = 2, HZ = 4, 11 chunks: 13 x 21 x 44 floats around the position the tile's centre voxel is displaced
+//           to (gw_origin: one dependent load per workgroup).  One channel's window is 48 KB: two workgroups per CU
+//           with one window each.  Any smooth displacement.
+//   GWNear  H = 1, 10 chunks: 11 x 19 x 40 floats = 33 440 B around the tile itself (gw_origin_near: nothing to load
+//           first), for samples less than a voxel from their own voxel -- the Euler step of a shoot.  Two of them per
+//           workgroup and two workgroups per CU are 133 760 B of the 160 KB, so the next channel's window can be in
+//           flight while this one is read.  Its last round of chunks is cut off at the window's end (GWLoader::issue).
 // Samples with a corner outside the window take their corners with the pair gathers (per lane, wave-uniform skip).
 #pragma once
 #include "common.hpp"
 
 namespace lago {
 
-struct GW {
 #ifndef LAGO_GW_TY
 #define LAGO_GW_TY 16
 #endif
-    static constexpr int TX = 8, TY = LAGO_GW_TY, TZ = 32, H = 2, HZ = 4;
+template <int H_, int HZ_, int WZC_, bool EXACT_>
+struct GWGeom {
+    static constexpr int TX = 8, TY = LAGO_GW_TY, TZ = 32, H = H_, HZ = HZ_;
     static constexpr int NT = 32 * TY;   // threads of a workgroup: lane = z, TY rows of y, one x slab, TX voxels per lane along x
-    static constexpr int WX = TX + 1 + 2 * H, WY = TY + 1 + 2 * H, WZC = 11, WZ = 4 * WZC;
+    static constexpr int WX = TX + 1 + 2 * H, WY = TY + 1 + 2 * H, WZC = WZC_, WZ = 4 * WZC;
     static constexpr int NCHUNK = WX * WY * WZC;
+    static constexpr bool EXACT = EXACT_;  // chunks past the window are not moved: the window takes NCHUNK * 16 bytes
     static constexpr uint32_t kOutside = 0x80000000u;  // beyond any plane (nvox * 8 < 2^32): reads 0
+    static_assert(WZ >= TZ + 1 + 2 * HZ + 3, "z rows: the origin is floored to a chunk boundary");
+    static_assert(WX * WY * WZ <= (1 << 14), "GWLerpT::pk keeps the window index in 14 bits");
     template <int NT>
     static constexpr int rounds() { return (NCHUNK + NT - 1) / NT; }
     template <int NT>
-    static constexpr size_t lds_bytes() { return (size_t)rounds<NT>() * NT * 16; }
+    static constexpr size_t lds_bytes() { return EXACT ? (size_t)NCHUNK * 16 : (size_t)rounds<NT>() * NT * 16; }
 };
+using GW = GWGeom<2, 4, 11, false>;
+using GWNear = GWGeom<1, 1, 10, true>;
 
 // launch decomposition: tiles of one batch item, z fastest
 struct GWGrid {
@@ -91,36 +103,51 @@ __device__ __forceinline__ GWOrigin gw_origin(const GWTile &t, const Geom &g, in
     o.oz = (t.z0 + (pz - czi) - GW::HZ) & ~3;  // floor to a chunk boundary
     return o;
 }
+// ... and of the untranslated window: the tile minus its halo
+__device__ __forceinline__ GWOrigin gw_origin_near(const GWTile &t) {
+    GWOrigin o;
+    o.ox = t.x0 - GWNear::H;
+    o.oy = t.y0 - GWNear::H;
+    o.oz = (t.z0 - GWNear::HZ) & ~3;
+    return o;
+}
 
 // The 16-byte chunks of the window this lane moves (the same for every channel): byte offsets into a plane.
-template <int NT>
+template <int NT, class G = GW>
 struct GWLoader {
-    uint32_t src[GW::rounds<NT>()];
+    uint32_t src[G::template rounds<NT>()];
     __device__ __forceinline__ void plan(const GWOrigin &o, const Geom &g) {
 #pragma unroll
-        for (int r = 0; r < GW::rounds<NT>(); ++r) {
+        for (int r = 0; r < G::template rounds<NT>(); ++r) {
             const uint32_t c = (uint32_t)(r * NT) + threadIdx.x;
-            const uint32_t row = c / (uint32_t)GW::WZC, cz = c - row * GW::WZC;
-            const uint32_t wx = row / (uint32_t)GW::WY, wy = row - wx * GW::WY;
+            const uint32_t row = c / (uint32_t)G::WZC, cz = c - row * G::WZC;
+            const uint32_t wx = row / (uint32_t)G::WY, wy = row - wx * G::WY;
             const int gx = o.ox + (int)wx, gy = o.oy + (int)wy, gz = o.oz + 4 * (int)cz;
-            const bool ok = c < (uint32_t)GW::NCHUNK && (uint32_t)gx < (uint32_t)g.nx && (uint32_t)gy < (uint32_t)g.ny &&
+            const bool ok = c < (uint32_t)G::NCHUNK && (uint32_t)gx < (uint32_t)g.nx && (uint32_t)gy < (uint32_t)g.ny &&
                             (uint32_t)gz < (uint32_t)g.nz;
-            src[r] = ok ? (((uint32_t)gx * (uint32_t)g.ny + (uint32_t)gy) * (uint32_t)g.nz + (uint32_t)gz) * 4u : GW::kOutside;
+            src[r] = ok ? (((uint32_t)gx * (uint32_t)g.ny + (uint32_t)gy) * (uint32_t)g.nz + (uint32_t)gz) * 4u : G::kOutside;
         }
     }
     // `plane` is wave-uniform; chunk c lands at win + 4 c floats (lane l of a wave at the wave's base + 16 l bytes)
     __device__ __forceinline__ void issue(const float *__restrict__ plane, uint32_t plane_bytes, float *win) const {
         const BufRsrc r = make_rsrc(plane, plane_bytes);
 #pragma unroll
-        for (int q = 0; q < GW::rounds<NT>(); ++q) {
+        for (int q = 0; q < G::template rounds<NT>(); ++q) {
             float *dst = win + (size_t)(q * NT + (threadIdx.x & ~63u)) * 4;
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(r, (__attribute__((address_space(3))) void *)dst, 16, src[q], 0, 0, 0);
+            if (G::EXACT && (q + 1) * NT > G::NCHUNK) {
+                // lanes past the window's end stay out of the load: what lies behind the window is somebody else's
+                if ((uint32_t)(q * NT) + threadIdx.x < (uint32_t)G::NCHUNK)
+                    __builtin_amdgcn_raw_ptr_buffer_load_lds(r, (__attribute__((address_space(3))) void *)dst, 16, src[q], 0, 0, 0);
+            } else {
+                __builtin_amdgcn_raw_ptr_buffer_load_lds(r, (__attribute__((address_space(3))) void *)dst, 16, src[q], 0, 0, 0);
+            }
         }
     }
 };
 
 // One sample: the first lines of Lerp3::setup (same expressions), then window indices instead of byte offsets.
-struct GWLerp {
+template <class G>
+struct GWLerpT {
     float t, u, v;
     uint32_t pk;  // window index of (fx, fy, zb) | dX << 14 | dY << 15 | f_hi << 16 | c_lo << 17
     // returns false if a corner lies outside the window
@@ -136,9 +163,9 @@ struct GWLerp {
         const bool f_hi = fz != zb, c_lo = cz == zb;
         const int ax = fx - o.ox, ay = fy - o.oy, az = zb - o.oz;
         // branch-free: (unsigned)a <= (unsigned)b folds the two-sided tests (fx <= cx <= fx + 1)
-        const bool in = ((uint32_t)ax < (uint32_t)(GW::WX - (cx - fx))) & ((uint32_t)ay < (uint32_t)(GW::WY - (cy - fy))) &
-                        ((uint32_t)az < (uint32_t)(GW::WZ - 1));
-        const uint32_t wi = in ? (uint32_t)((ax * GW::WY + ay) * GW::WZ + az) : 0u;
+        const bool in = ((uint32_t)ax < (uint32_t)(G::WX - (cx - fx))) & ((uint32_t)ay < (uint32_t)(G::WY - (cy - fy))) &
+                        ((uint32_t)az < (uint32_t)(G::WZ - 1));
+        const uint32_t wi = in ? (uint32_t)((ax * G::WY + ay) * G::WZ + az) : 0u;
         pk = wi | (cx != fx ? 1u << 14 : 0u) | (cy != fy ? 1u << 15 : 0u) | (f_hi ? 1u << 16 : 0u) | (c_lo ? 1u << 17 : 0u);
         // pin the packed word here: otherwise its ingredients (six coordinates per sample) are kept alive up to the
         // first use behind the barrier
@@ -150,7 +177,7 @@ struct GWLerp {
         uint32_t p = pk;
         asm volatile("" : "+v"(p));  // rebuild the four addresses per channel; keeping them costs 4 VGPRs per sample
         const uint32_t b0 = p & 0x3fffu;
-        const uint32_t dX = (p & (1u << 14)) ? (uint32_t)(GW::WY * GW::WZ) : 0u, dY = (p & (1u << 15)) ? (uint32_t)GW::WZ : 0u;
+        const uint32_t dX = (p & (1u << 14)) ? (uint32_t)(G::WY * G::WZ) : 0u, dY = (p & (1u << 15)) ? (uint32_t)G::WZ : 0u;
         const bool f_hi = p & (1u << 16), c_lo = p & (1u << 17);
         const uint32_t rb[4] = {b0, b0 + dX, b0 + dX + dY, b0 + dY};
         float lo[4], hi[4];
@@ -159,5 +186,6 @@ struct GWLerp {
         return lerp3_pairs(lo, hi, t, u, v, f_hi, c_lo);
     }
 };
+using GWLerp = GWLerpT<GW>;
 
 }  // namespace lago

@@ -54,9 +54,11 @@ class ComposeFunction(torch.autograd.Function):
     arguments are vector fields of the same shape; bit-identical to the unfused expression."""
 
     @staticmethod
-    def forward(ctx, u, v, ds, dt):
+    def forward(ctx, u, v, ds, dt, near_identity=False):
         ctx.ds, ctx.dt = ds, dt
         ctx.save_for_backward(u, v)
+        if near_identity and u.is_cuda:   # the hint is for the device kernels (a CPU stand-in of the extension has none)
+            return lagomorph_ext.compose(u.contiguous(), v.contiguous(), ds, dt, near_identity=True)
         return lagomorph_ext.compose(u.contiguous(), v.contiguous(), ds, dt)
 
     @staticmethod
@@ -68,24 +70,25 @@ class ComposeFunction(torch.autograd.Function):
             # d_u = (D_u interp)^T grad + ds * grad in one kernel (the sum of each voxel's d_u starts from ds * grad)
             d_v, d_u = lagomorph_ext.interp_backward_fused(gradout, v.contiguous(), u.contiguous(), ctx.ds, need_v,
                                                            addgo=ctx.ds)
-            return d_u, d_v if need_v else None, None, None
+            return d_u, d_v if need_v else None, None, None, None
         gi = gradout if ctx.dt == 1.0 else ctx.dt * gradout  # gradient reaching the interp output
         d_v, d_u = lagomorph_ext.interp_backward(gi, v.contiguous(), u.contiguous(), ctx.ds, need_v, need_u)
         if need_u:
             d_u.add_(gradout, alpha=ctx.ds)  # d_u is a fresh tensor owned by this call
-        return d_u, d_v, None, None
+        return d_u, d_v, None, None, None
 
 
-def compose(u, v, ds=1.0, dt=1.0):
-    """ds*u(x) + dt*v(x + ds*u(x))   (deform.py:53-55)"""
+def compose(u, v, ds=1.0, dt=1.0, near_identity=False):
+    """ds*u(x) + dt*v(x + ds*u(x))   (deform.py:53-55).  `near_identity`: the caller expects |ds*u| below one voxel
+    (a speed hint to the fused kernel, lagomorph_ext.compose; never a different value)."""
     if u.shape == v.shape and u.size(1) == u.dim() - 2 and u.dtype == v.dtype:
-        return ComposeFunction.apply(u, v, ds, dt)
+        return ComposeFunction.apply(u, v, ds, dt, near_identity)
     return ds * u + dt * interp(v, u, dt=ds)
 
 
 def compose_disp_vel(u, v, dt=1.0):
-    """dt*v(x) + u(x + dt*v(x))   (deform.py:58-62)"""
-    return compose(v, u, ds=dt, dt=1.0)
+    """dt*v(x) + u(x + dt*v(x))   (deform.py:58-62) -- the Euler step of an integration: dt*v is a fraction of a voxel"""
+    return compose(v, u, ds=dt, dt=1.0, near_identity=True)
 
 
 def compose_vel_disp(v, u, dt=1.0):

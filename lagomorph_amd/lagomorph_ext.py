@@ -63,6 +63,7 @@ _SIGS = {
     "lago_regrid_backward_sep": [_vp, _vp, _vp, _i64, _int, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _vp, _vp, _vp],
     "lago_regrid_backward": [_vp, _vp, _int, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _vp, _vp, _vp],
     "lago_compose": [_vp, _vp, _vp, _dbl, _dbl, _int, _i64, _i64, _i64, _i64, _vp],
+    "lago_compose_near": [_vp, _vp, _vp, _dbl, _dbl, _int, _i64, _i64, _i64, _i64, _vp],
     "lago_lincomb": [_vp, _int, _vp, _vp, _vp, _vp, _dbl, _dbl, _dbl, _dbl, _i64, _vp],
     "lago_Ad_star": [_vp, _vp, _vp, _vp, _int, _i64, _i64, _i64, _i64, _vp],
     "lago_interp_backward_fused": [_vp, _vp, _vp, _vp, _vp, _dbl, _int, _i64, _i64, _i64, _i64, _i64, _int, _int, _int, _int,
@@ -106,7 +107,7 @@ class LagoTuning(ctypes.Structure):
                 ("vector_kernels", ctypes.c_int32), ("launch_order", ctypes.c_int32), ("stencil_tile", ctypes.c_int32),
                 ("gather_window", ctypes.c_int32), ("fluid_mode", ctypes.c_int32), ("fluid_xpass_ipw", ctypes.c_int32),
                 ("fluid_zy_persist", ctypes.c_int32), ("fluid_xpass_wide", ctypes.c_int32),
-                ("fluid_xpass_persist", ctypes.c_int32), ("affine_box", ctypes.c_int32)]
+                ("fluid_xpass_persist", ctypes.c_int32), ("affine_box", ctypes.c_int32), ("compose_near", ctypes.c_int32)]
 
 
 _lib.lago_get_tuning.argtypes = [ctypes.POINTER(LagoTuning)]
@@ -268,7 +269,8 @@ def set_stencil_tile(on):
 _lib.lago_path_launches.restype = ctypes.c_longlong
 _lib.lago_path_launches.argtypes = [_int]
 PATHS = ("gather_window", "stencil_tile", "vector_gather", "splat_shear", "splat_shear_mc", "splat_tiled", "splat_global",
-         "fluid_lds", "fluid_2d", "fluid_xpass", "fluid_rocfft", "splat_2d", "splat_affine_box", "fluid_generic")  # LAGO_PATH_* of include/lagomorph_hip.h, in order
+         "fluid_lds", "fluid_2d", "fluid_xpass", "fluid_rocfft", "splat_2d", "splat_affine_box", "fluid_generic",
+         "gather_window_near")  # LAGO_PATH_* of include/lagomorph_hip.h, in order
 
 
 _lib.lago_reversed_launches.restype = ctypes.c_longlong
@@ -293,9 +295,19 @@ def set_gather_window(on):
     tune(gather_window=1 if on else 0)
 
 
+def set_compose_near(on):
+    """1 (default): `compose(..., near_identity=True)` takes the fixed-origin LDS-window kernel with two windows in flight
+    where the shape allows the window kernels; 0: the hint is ignored.  Same bits."""
+    tune(compose_near=1 if on else 0)
+
+
 if os.environ.get("LAGO_GATHER_WINDOW") is not None:  # profiling convenience: A/B under rocprofv3 without code changes
     # (parsed defensively: an empty or odd value of a profiling variable must not break `import lagomorph_amd`)
     set_gather_window(os.environ["LAGO_GATHER_WINDOW"].strip().lower() not in ("", "0", "off", "false", "no"))
+
+
+if os.environ.get("LAGO_COMPOSE_NEAR") is not None:  # the same convenience for the near-identity arm of compose
+    set_compose_near(os.environ["LAGO_COMPOSE_NEAR"].strip().lower() not in ("", "0", "off", "false", "no"))
 
 
 def set_vector_kernels(on):
@@ -886,10 +898,11 @@ def _overlaps(a, b):
     return a.numel() > 0 and b.numel() > 0 and a0 < b0 + b.numel() * b.element_size() and b0 < a0 + a.numel() * a.element_size()
 
 
-def compose(u, v, ds=1.0, dt=1.0, out=None):
+def compose(u, v, ds=1.0, dt=1.0, out=None, near_identity=False):
     """Fused deform.compose (deform.py:53-55): ds*u + dt*interp(v, u, dt=ds) in one kernel.
     Not part of the reference's extension surface; u and v are (N, d, *spatial) vector fields.  `out`: a contiguous
-    tensor of their shape to write into (it must not alias u or v)."""
+    tensor of their shape to write into (it must not alias u or v).  `near_identity`: a hint that |ds*u| stays below one
+    voxel (the Euler step of a shoot); it selects a kernel (`set_compose_near`), never a value."""
     _check_input(u, "u")
     _check_input(v, "v")
     _same(u, v)
@@ -905,7 +918,8 @@ def compose(u, v, ds=1.0, dt=1.0, out=None):
         _same(u, out)
         if out.shape != u.shape or _overlaps(out, u) or _overlaps(out, v):
             raise RuntimeError("compose: out must have the shape of u and must not alias an input")
-    _call("lago_compose", u, _ptr(out), _ptr(u), _ptr(v), float(ds), float(dt), dim, u.size(0), nx, ny, nz)
+    _call("lago_compose_near" if near_identity else "lago_compose", u, _ptr(out), _ptr(u), _ptr(v), float(ds), float(dt), dim,
+          u.size(0), nx, ny, nz)
     return out
 
 

@@ -110,7 +110,7 @@ def _shoot(metric, m0, phiinv, dt, num_steps, v0, keep, out=None):
             m, mphi = lagomorph_ext.Ad_star(phi, m0), None
         v = metric.sharp(m)
         del m
-        nxt = lagomorph_ext.compose(v, phi, -dt, 1.0, out=out if k + 1 == general else None)
+        nxt = lagomorph_ext.compose(v, phi, -dt, 1.0, out=out if k + 1 == general else None, near_identity=True)
         if keep:
             steps.append((phi, v, mphi))
         phi = nxt
