@@ -50,6 +50,11 @@ extern "C" {
 #define LAGO_MI_MAX_BINS 64
 #define LAGO_MI_FRAC_BITS 32
 
+/* lago_warp_labels: how the label of a sample is chosen; lago_label_overlap: the most labels a count table takes */
+#define LAGO_LABELS_NEAREST 0
+#define LAGO_LABELS_VOTE 1
+#define LAGO_LABELS_MAX 4096
+
 /* ---- housekeeping --------------------------------------------------------- */
 
 /* replaces set_debug_mode (extension.cpp:105-107): when non-zero every entry
@@ -377,7 +382,23 @@ long long lago_reversed_launches(void);
      * other output.  Errors and empty extents as for lago_mi_histogram.  No counterpart in the reference. */       \
     int lago_mi_backward##SUF(REAL *dI, REAL *dJ, const double *G, const REAL *I, const REAL *J, int bins,          \
                               double loI, double hiI, double loJ, double hiJ, int dim, int64_t rows, int64_t nx,    \
-                              int64_t ny, int64_t nz, void *stream);
+                              int64_t ny, int64_t nz, void *stream);                                                \
+    /* lago_warp_labels: out(x) = the label of L at x + dt u(x).  L: (broadcast ? 1 : nn, 1, sp) int32 label VALUES \
+     * (any bit pattern), u: (nn, dim, sp), out: (nn, 1, sp) int32.  Per axis with extent n and voxel index i:      \
+     *       p = i + dt u in REAL, the position lago_interp_forward samples at, bit for bit                         \
+     *       p = fmin(fmax(p, -1), n)   (out of range, infinite and saturated positions fall on the border voxel,   \
+     *                                   a NaN on the first voxel of the axis; no in-range position changes)        \
+     *       f = floor(p), t = p - f    (in REAL, then widened to double)                                           \
+     *       corners clamp(f, 0, n - 1) and clamp(f + 1, 0, n - 1)                                                  \
+     * LAGO_LABELS_NEAREST: per axis the upper corner where t > 0.5, else the lower (a tie goes to the lower).      \
+     * LAGO_LABELS_VOTE: the 2^dim corners, first axis slowest, weigh w_q = (a_x a_y) a_z in double (a = 1 - t for  \
+     * the lower corner, t for the upper; a_y a_z in 2D); a label's score is the sum of w_q over the corners that   \
+     * carry it, q ascending from 0.0 (clamped corners that coincide each add); the largest score wins, among equal \
+     * scores the smallest label value.  Nothing is fused; no atomic: the same bits from call to call.              \
+     * LAGO_ERR_INVALID: a mode or dim that is none of the above, out overlapping an input.  Empty extents do       \
+     * nothing (LAGO_OK).  No counterpart in the reference. */                                                      \
+    int lago_warp_labels##SUF(int32_t *out, const int32_t *L, const REAL *u, double dt, int mode, int broadcast,    \
+                              int dim, int64_t nn, int64_t nx, int64_t ny, int64_t nz, void *stream);
 
 LAGO_DECLARE(float, _f32)
 LAGO_DECLARE(double, _f64)
@@ -386,6 +407,19 @@ LAGO_DECLARE(double, _f64)
  * row is cut into chunks of a few thousand voxels, as many as keep the scratch of all rows within 8 MB).  The caller
  * allocates rows x this x bins x bins 64-bit integers.  No counterpart in the reference. */
 int lago_mi_scratch_tables(int bins, int64_t rows, int64_t nvox);
+
+/* label_overlap: counts (rows, K, 3) of two label maps A, B (rows, nvox) of int32 label values, K = num_labels in
+ * 1..LAGO_LABELS_MAX: per row and label k in [0, K)  [#(A == k), #(B == k), #(A == k and B == k)]  as 64-bit integers.
+ * A voxel whose label is outside [0, K) counts in nothing for that image.  Workgroups count chunks of a row into 32-bit
+ * tables in LDS (a wave adds once for all its lanes that hold the same pair) and write them to `scratch`, rows x
+ * scratch_chunks x K x 3 32-bit integers that need not be initialised; a second kernel sums the chunks.  No global
+ * atomic: the same bits from call to call, for any chunking.  lago_label_overlap_scratch_chunks says how many chunks per
+ * row the call can use (>= 1: chunks of about 16384 voxels, as many as keep the scratch of all rows within 8 MB, or
+ * one table a row), fewer only cost speed.  counts and scratch may not overlap an input or each other; A may equal B.
+ * LAGO_ERR_INVALID: num_labels out of range, more than 2^30 voxels in a row.  No counterpart in the reference. */
+int lago_label_overlap(long long *counts, const int32_t *A, const int32_t *B, uint32_t *scratch, int64_t scratch_chunks,
+                       int num_labels, int64_t rows, int64_t nvox, void *stream);
+int lago_label_overlap_scratch_chunks(int num_labels, int64_t rows, int64_t nvox);
 
 /* ---- fused geometry operators (beyond the reference's extension surface) -------------
  * compose: out = ds*u + dt*interp(v, u, ds) in one pass -- deform.compose

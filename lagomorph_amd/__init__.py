@@ -19,6 +19,7 @@ if not _BUILDING:
     from .diff import (JacobianDeterminantFunction, JacobianTimesVectorFieldAdjointFunction,  # noqa: F401
                        JacobianTimesVectorFieldFunction, jacobian_determinant, jacobian_times_vectorfield,
                        jacobian_times_vectorfield_adjoint)
+    from .labels import dice, label_overlap, warp_labels  # noqa: F401
     from .lagomorph_ext import set_debug_mode  # noqa: F401
     from .lddmm import EPDiff_step, LDDMMAtlasBuilder, expmap, expmap_advect, lddmm_step, shard_indices  # noqa: F401
     from .metric import FluidMetric, FluidMetricOperator, GaussianMetric, Metric  # noqa: F401

@@ -81,6 +81,7 @@ _SIGS = {
     "lago_lncc_combine": [_vp, _vp, _vp, _vp, _vp, _int, _i64, _vp],
     "lago_mi_histogram": [_vp, _vp, _vp, _vp, _i64, _int, _dbl, _dbl, _dbl, _dbl, _int, _i64, _i64, _i64, _i64, _vp],
     "lago_mi_backward": [_vp, _vp, _vp, _vp, _vp, _int, _dbl, _dbl, _dbl, _dbl, _int, _i64, _i64, _i64, _i64, _vp],
+    "lago_warp_labels": [_vp, _vp, _vp, _dbl, _int, _int, _int, _i64, _i64, _i64, _i64, _vp],
     "lago_fluid_metric": [_vp, _vp, _vp, _i64, _int, _vp, _vp, _vp, _vp, _vp, _vp, _dbl, _dbl, _dbl, _int, _i64, _i64,
                           _i64, _i64, _vp],
     "lago_fluid_metric_scaled": [_vp, _vp, _vp, _i64, _int, _vp, _vp, _vp, _vp, _vp, _vp, _dbl, _dbl, _dbl, _int, _i64,
@@ -98,6 +99,10 @@ for _name, _args in _SIGS.items():
 _lib.lago_set_debug.argtypes = [_int]
 _lib.lago_mi_scratch_tables.argtypes = [_int, _i64, _i64]
 _lib.lago_mi_scratch_tables.restype = _int
+_lib.lago_label_overlap.argtypes = [_vp, _vp, _vp, _vp, _i64, _int, _i64, _i64, _vp]
+_lib.lago_label_overlap.restype = _int
+_lib.lago_label_overlap_scratch_chunks.argtypes = [_int, _i64, _i64]
+_lib.lago_label_overlap_scratch_chunks.restype = _int
 
 
 class LagoTuning(ctypes.Structure):
@@ -198,7 +203,10 @@ def _spatial(t):
 
 def _call(name, ref, *args):
     """Launch on torch's current stream of ref's device; raise RuntimeError on failure."""
-    f = _fn[name + _suffix(ref)]
+    _launch(_fn[name + _suffix(ref)], ref, *args)
+
+
+def _launch(f, ref, *args):
     if ref.device.index != torch.cuda.current_device():
         with torch.cuda.device(ref.device):
             rc = f(*args, torch.cuda.current_stream().cuda_stream)
@@ -759,6 +767,102 @@ def mi_backward(G, I, J, bins, range_I, range_J, need_I=True, need_J=True):
     _call("lago_mi_backward", I, _ptr(d_I), _ptr(d_J), _ptr(G), _ptr(I), _ptr(J), bins, loI, hiI, loJ, hiJ, dim,
           I.size(0) * I.size(1), nx, ny, nz)
     return d_I, d_J
+
+
+LABEL_MODES = {"nearest": 0, "vote": 1}   # LAGO_LABELS_NEAREST / LAGO_LABELS_VOTE of include/lagomorph_hip.h
+LABELS_MAX = 4096                         # LAGO_LABELS_MAX
+_LABEL_DTYPES = (torch.uint8, torch.int16, torch.int32, torch.int64)
+
+
+def label_mode(mode):
+    if not isinstance(mode, str) or mode not in LABEL_MODES:
+        raise ValueError(f"warp_labels: mode must be one of {sorted(LABEL_MODES)} (got {mode!r})")
+    return LABEL_MODES[mode]
+
+
+def label_count(num_labels):
+    try:
+        ok = not isinstance(num_labels, bool) and int(num_labels) == num_labels and 1 <= int(num_labels) <= LABELS_MAX
+    except (TypeError, ValueError):
+        ok = False
+    if not ok:
+        raise ValueError(f"label_overlap: num_labels must be an integer in 1..{LABELS_MAX} (got {num_labels!r})")
+    return int(num_labels)
+
+
+def _check_labels(x, name):
+    """A label map (N, 1, *sp) of an integer dtype; the device checks come last (_check_input), so that every error of
+    shape, dtype, mode or label count is raised whatever device the tensors are on."""
+    if not isinstance(x, torch.Tensor):
+        raise TypeError(f"{name} must be a torch.Tensor")
+    if x.dtype not in _LABEL_DTYPES:
+        raise RuntimeError(f"{name} must hold integer labels (uint8, int16, int32 or int64), got dtype {x.dtype}")
+    if x.dim() not in (4, 5) or x.size(1) != 1:
+        raise RuntimeError(f"{name} must be a label map of shape (N, 1, *spatial) with two or three spatial axes, "
+                           f"got shape {tuple(x.shape)}")
+
+
+def _as_int32(x):
+    return x if x.dtype == torch.int32 else x.to(torch.int32)
+
+
+def warp_labels(L, u, dt=1.0, mode="vote"):
+    """out(x) = the label of L at x + dt u(x): L (N or 1, 1, *sp) integer label VALUES, u (N, d, *sp) float32 or
+    float64, out (N, 1, *sp) in L's dtype.  mode "nearest" or "vote" (the label with the largest sum of multilinear
+    corner weights, the smallest label among equal sums); the definition is in include/lagomorph_hip.h
+    (csrc/labels.hip: warp_labels_kernel, warp_labels3_unroll_kernel).  The call takes int32: other dtypes are
+    converted and converted back, and values of an int64 tensor outside the int32 range are the caller's error (not
+    checked: that would synchronise).  Not differentiable.  Not in the reference; no CPU path."""
+    mode = label_mode(mode)
+    _check_labels(L, "L")
+    if not isinstance(u, torch.Tensor):
+        raise TypeError("u must be a torch.Tensor")
+    _suffix(u)
+    dim = L.dim() - 2
+    if u.dim() != L.dim() or u.size(1) != dim or tuple(u.shape[2:]) != tuple(L.shape[2:]):
+        raise RuntimeError(f"warp_labels: displacement of shape {tuple(u.shape)} does not match labels {tuple(L.shape)}")
+    nn = u.size(0)
+    if L.size(0) not in (1, nn):
+        raise RuntimeError("warp_labels: batch sizes of L and u are incompatible")
+    if L.device != u.device:
+        raise RuntimeError(f"lagomorph_ext: device mismatch ({L.device} vs {u.device})")
+    _check_input(L, "L")
+    _check_input(u, "u")
+    bc = L.size(0) < nn
+    _, nx, ny, nz = _spatial(L)
+    L32 = _as_int32(L)
+    out = torch.empty((nn, 1) + tuple(L.shape[2:]), dtype=torch.int32, device=L.device)
+    _call("lago_warp_labels", u, _ptr(out), _ptr(L32), _ptr(u), float(dt), mode, int(bc), dim, nn, nx, ny, nz)
+    return out if L.dtype == torch.int32 else out.to(L.dtype)
+
+
+def label_overlap_chunks(num_labels, rows, nvox):
+    """Partial tables per row label_overlap uses (lago_label_overlap_scratch_chunks)."""
+    return int(_lib.lago_label_overlap_scratch_chunks(num_labels, rows, nvox))
+
+
+def label_overlap(A, B, num_labels):
+    """int64 counts (N, K, 3) of two label maps A, B (N, 1, *sp): per item and label k in [0, K = num_labels)
+    [#(A == k), #(B == k), #(A == k and B == k)]; a voxel whose label is outside [0, K) counts in nothing for that
+    image.  Integer sums in LDS tables and a slab of partial tables allocated here, no atomic on memory: the same
+    bits from call to call (csrc/labels.hip: label_overlap_kernel, label_overlap_reduce_kernel).  Labels go to the
+    call as int32 (see warp_labels).  Not in the reference; no CPU path."""
+    K = label_count(num_labels)
+    _check_labels(A, "A")
+    _check_labels(B, "B")
+    if B.shape != A.shape:
+        raise RuntimeError(f"label_overlap: A {tuple(A.shape)} and B {tuple(B.shape)} must have the same shape")
+    _same(A, B)
+    _check_input(A, "A")
+    _check_input(B, "B")
+    rows, nvox = A.size(0), A[0].numel()
+    A32 = _as_int32(A)
+    B32 = A32 if B is A else _as_int32(B)
+    counts = torch.empty((rows, K, 3), dtype=torch.int64, device=A.device)
+    chunks = label_overlap_chunks(K, rows, nvox)
+    scratch = torch.empty((rows * chunks * K * 3,), dtype=torch.int32, device=A.device)
+    _launch(_lib.lago_label_overlap, A, _ptr(counts), _ptr(A32), _ptr(B32), _ptr(scratch), chunks, K, rows, nvox)
+    return counts
 
 
 def fluid_operator(Fmv, inverse, cosluts, sinluts, alpha, beta, gamma):
