@@ -398,7 +398,36 @@ long long lago_reversed_launches(void);
      * LAGO_ERR_INVALID: a mode or dim that is none of the above, out overlapping an input.  Empty extents do       \
      * nothing (LAGO_OK).  No counterpart in the reference. */                                                      \
     int lago_warp_labels##SUF(int32_t *out, const int32_t *L, const REAL *u, double dt, int mode, int broadcast,    \
-                              int dim, int64_t nn, int64_t nx, int64_t ny, int64_t nz, void *stream);
+                              int dim, int64_t nn, int64_t nx, int64_t ny, int64_t nz, void *stream);            \
+    /* lago_interp_points: a field sampled at a list of positions.  out[n,c,p] = lerp(F[n or 0,c], x[n,:,p]).       \
+     * F: (broadcast_F ? 1 : nn, nc, sp)  x: (nn, dim, np), channel-first, in voxel-index units along the spatial   \
+     * axes in order (a field (nn, dim, sp) viewed as (nn, dim, nvox) is a point set)  out: (nn, nc, np).  The      \
+     * arithmetic is lago_interp_forward's at the same position, expression for expression and bit for bit:        \
+     * f = floor(x) saturated to +-2^30, t = x - f, corners clamp(f, 0, n - 1) and clamp(f + 1, 0, n - 1), the same \
+     * fma nesting.  So a position outside the grid reads the clamped border, the domain is |x| < 2^30, and a       \
+     * coordinate that is not finite gives NaN for that point and never an access outside F (every corner index is \
+     * clamped before it is used).  One gather pass, no atomics: the same bits from call to call.                  \
+     * LAGO_ERR_INVALID before any device call: dim not 2 or 3, a negative extent, a channel plane of 2^32 bytes or \
+     * more, np >= 2^31, nn > 65535, out overlapping an input.  nn, nc, np or an extent equal to 0: nothing is done \
+     * (LAGO_OK).  No counterpart in the reference. */                                                              \
+    int lago_interp_points##SUF(REAL *out, const REAL *F, const REAL *x, int dim, int64_t nn, int64_t nc,           \
+                                int64_t np, int64_t nx, int64_t ny, int64_t nz, int broadcast_F, void *stream);     \
+    /* its gradients for an upstream grad_out (nn, nc, np).  Either output may be NULL when it is not needed        \
+     * (need_F / need_x 0): it is then neither computed nor written.                                                \
+     *   d_x (nn, dim, np): d_x[n,a,p] = sum_c grad_out[n,c,p] dF_c/dx_a, the position gradient of the multilinear  \
+     *     value on the fetched corners as lago_interp_backward's d_u forms it, c ascending: the c = 0 product, then \
+     *     one fma per channel.  The one-sided derivative of the cell floor(x); zero along an axis on which both    \
+     *     clamped corners coincide.  Plain stores, no atomic: the same bits from call to call.                     \
+     *   d_F like F (summed over the items when broadcast_F): zeroed on the stream, then every point adds w_q g to  \
+     *     its 2^dim clamped corners, w_q = (a_x a_y) a_z in REAL (a = 1 - t for the lower corner, t for the upper; \
+     *     a_y a_z for dim 2), the product w_q g rounded once.  The adds are hardware float atomics on memory: the  \
+     *     LAST BITS of d_F depend on their arrival order and differ from call to call, as lago_interp_backward's   \
+     *     d_I.  Cells that receive nothing hold exactly 0.                                                         \
+     * Errors and empty problems as for lago_interp_points (with np == 0 a wanted d_F is zeroed); an output may not \
+     * overlap an input or the other output.  No counterpart in the reference. */                                   \
+    int lago_interp_points_backward##SUF(REAL *d_F, REAL *d_x, const REAL *grad_out, const REAL *F, const REAL *x,  \
+                                         int dim, int64_t nn, int64_t nc, int64_t np, int64_t nx, int64_t ny,       \
+                                         int64_t nz, int broadcast_F, int need_F, int need_x, void *stream);
 
 LAGO_DECLARE(float, _f32)
 LAGO_DECLARE(double, _f64)

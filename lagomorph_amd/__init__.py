@@ -23,6 +23,7 @@ if not _BUILDING:
     from .lagomorph_ext import set_debug_mode  # noqa: F401
     from .lddmm import EPDiff_step, LDDMMAtlasBuilder, expmap, expmap_advect, lddmm_step, shard_indices  # noqa: F401
     from .metric import FluidMetric, FluidMetricOperator, GaussianMetric, Metric  # noqa: F401
+    from .points import InterpPointsFunction, deform_points, interp_points, landmark_distance  # noqa: F401
     from .similarity import (JointHistogramFunction, LNCCFunction, LNCCSimilarity, MISimilarity,  # noqa: F401
                              joint_histogram, lncc, lncc_loss, mi_loss, mutual_information)
     from .smooth import GaussianSmoothFunction, gaussian_smooth, gaussian_taps  # noqa: F401

@@ -82,6 +82,8 @@ _SIGS = {
     "lago_mi_histogram": [_vp, _vp, _vp, _vp, _i64, _int, _dbl, _dbl, _dbl, _dbl, _int, _i64, _i64, _i64, _i64, _vp],
     "lago_mi_backward": [_vp, _vp, _vp, _vp, _vp, _int, _dbl, _dbl, _dbl, _dbl, _int, _i64, _i64, _i64, _i64, _vp],
     "lago_warp_labels": [_vp, _vp, _vp, _dbl, _int, _int, _int, _i64, _i64, _i64, _i64, _vp],
+    "lago_interp_points": [_vp, _vp, _vp, _int, _i64, _i64, _i64, _i64, _i64, _i64, _int, _vp],
+    "lago_interp_points_backward": [_vp, _vp, _vp, _vp, _vp, _int, _i64, _i64, _i64, _i64, _i64, _i64, _int, _int, _int, _vp],
     "lago_fluid_metric": [_vp, _vp, _vp, _i64, _int, _vp, _vp, _vp, _vp, _vp, _vp, _dbl, _dbl, _dbl, _int, _i64, _i64,
                           _i64, _i64, _vp],
     "lago_fluid_metric_scaled": [_vp, _vp, _vp, _i64, _int, _vp, _vp, _vp, _vp, _vp, _vp, _dbl, _dbl, _dbl, _int, _i64,
@@ -863,6 +865,68 @@ def label_overlap(A, B, num_labels):
     scratch = torch.empty((rows * chunks * K * 3,), dtype=torch.int32, device=A.device)
     _launch(_lib.lago_label_overlap, A, _ptr(counts), _ptr(A32), _ptr(B32), _ptr(scratch), chunks, K, rows, nvox)
     return counts
+
+
+def _check_points(F, x, what, grad_out=None, backward=False):
+    """A field F (N or 1, C, *sp) with two or three spatial axes and a point set x (N, d, P), d = len(sp), of one
+    floating dtype (and, for the backward, grad_out (N, C, P)); returns (dim, nn, broadcast).  Every error of type,
+    dtype, shape, batch and contiguity is raised whatever device the tensors are on; the device checks come last."""
+    named = (("F", F), ("x", x)) + ((("grad_out", grad_out),) if backward else ())
+    for name, t in named:
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"{name} must be a torch.Tensor")
+    for name, t in named:
+        _suffix(t)
+    for name, t in named[1:]:
+        if t.dtype != F.dtype:
+            raise RuntimeError(f"lagomorph_ext: dtype mismatch ({F.dtype} vs {t.dtype})")
+    dim = F.dim() - 2
+    if dim not in (2, 3):
+        raise RuntimeError(f"{what}: F must be a field of shape (N, C, *spatial) with two or three spatial axes, "
+                           f"got shape {tuple(F.shape)}")
+    if x.dim() != 3 or x.size(1) != dim:
+        raise RuntimeError(f"{what}: x must be a point set of shape (N, {dim}, P) for a field with {dim} spatial axes, "
+                           f"got shape {tuple(x.shape)}")
+    nn = x.size(0)
+    if F.size(0) not in (1, nn):
+        raise RuntimeError(f"{what}: batch sizes of F ({F.size(0)}) and x ({nn}) are incompatible")
+    if backward and tuple(grad_out.shape) != (nn, F.size(1), x.size(2)):
+        raise RuntimeError(f"{what}: grad_out of shape {tuple(grad_out.shape)} does not match the output "
+                           f"{(nn, F.size(1), x.size(2))}")
+    for name, t in named:
+        if not t.is_contiguous():
+            raise RuntimeError(f"{name} must be contiguous")
+    for name, t in named[1:]:
+        if t.device != F.device:
+            raise RuntimeError(f"lagomorph_ext: device mismatch ({F.device} vs {t.device})")
+    for name, t in named:
+        _check_input(t, name)
+    return dim, nn, F.size(0) < nn
+
+
+def interp_points_forward(F, x):
+    """out (N, C, P): F (N or 1, C, *sp) sampled multilinearly at the positions x (N, d, P), in voxel-index units;
+    lago_interp_points of include/lagomorph_hip.h (csrc/points.hip: interp_points_fwd_kernel).  Not in the reference;
+    no CPU path."""
+    dim, nn, bc = _check_points(F, x, "interp_points")
+    _, nx, ny, nz = _spatial(F)
+    out = torch.empty((nn, F.size(1), x.size(2)), dtype=F.dtype, device=F.device)
+    _call("lago_interp_points", F, _ptr(out), _ptr(F), _ptr(x), dim, nn, F.size(1), x.size(2), nx, ny, nz, int(bc))
+    return out
+
+
+def interp_points_backward(grad_out, F, x, need_F, need_x):
+    """[d_F like F or None, d_x like x or None] for grad_out (N, C, P): lago_interp_points_backward
+    (csrc/points.hip: interp_points_bwd_kernel).  A gradient that is not needed is not computed.  d_F is a sum of
+    hardware float atomics (its last bits differ from call to call), d_x repeats bit for bit."""
+    dim, nn, bc = _check_points(F, x, "interp_points_backward", grad_out, backward=True)
+    _, nx, ny, nz = _spatial(F)
+    d_F = torch.empty_like(F) if need_F else None
+    d_x = torch.empty_like(x) if need_x else None
+    if need_F or need_x:
+        _call("lago_interp_points_backward", F, _ptr(d_F), _ptr(d_x), _ptr(grad_out), _ptr(F), _ptr(x), dim, nn,
+              F.size(1), x.size(2), nx, ny, nz, int(bc), int(bool(need_F)), int(bool(need_x)))
+    return [d_F, d_x]
 
 
 def fluid_operator(Fmv, inverse, cosluts, sinluts, alpha, beta, gamma):
