@@ -427,7 +427,49 @@ long long lago_reversed_launches(void);
      * overlap an input or the other output.  No counterpart in the reference. */                                   \
     int lago_interp_points_backward##SUF(REAL *d_F, REAL *d_x, const REAL *grad_out, const REAL *F, const REAL *x,  \
                                          int dim, int64_t nn, int64_t nc, int64_t np, int64_t nx, int64_t ny,       \
-                                         int64_t nz, int broadcast_F, int need_F, int need_x, void *stream);
+                                         int64_t nz, int broadcast_F, int need_F, int need_x, void *stream);         \
+    /* lago_bspline_prefilter: samples -> cubic B-spline coefficients.  in, out: (rows, sp), rows = batch items      \
+     * times channels.  Per spatial axis of extent n > 1, axes in order, c solves B c = f with B the (1, 4, 1) / 6    \
+     * tridiagonal under a whole-sample mirror of period 2n - 2 (first row (4, 2) / 6, last row (2, 4) / 6): pole    \
+     * z = sqrt(3) - 2, gain 6, c+[0] = sum_k z^k 6 f[mirror k] / (1 - z^(2n-2)) (cut where |z|^k is below half an   \
+     * ulp), c+[i] = 6 f[i] + z c+[i-1], c[n-1] = z / (z^2 - 1) (c+[n-1] + z c+[n-2]), c[i] = z (c[i+1] - c+[i]).    \
+     * adjoint != 0: B^T instead of B (= D B D^-1, D = diag(1/2, 1, ..., 1, 1/2): the end samples of every line      \
+     * doubled before its pass and halved after it; the same for n <= 2).  One launch per axis, the first from in    \
+     * to out and the others in place on out; lines up to 256 samples are staged in LDS, longer ones run in place    \
+     * through global memory.  8 bytes per element and pass (float32), no atomics: the same bits from call to call.  \
+     * LAGO_ERR_INVALID before any device call: dim not 2 or 3, a negative extent, a plane of 2^29 elements or more, \
+     * out overlapping in, a null pointer.  rows or an extent equal to 0: nothing is done (LAGO_OK).  No counterpart \
+     * in the reference. */                                                                                          \
+    int lago_bspline_prefilter##SUF(REAL *out, const REAL *in, int adjoint, int dim, int64_t rows, int64_t nx,        \
+                                    int64_t ny, int64_t nz, void *stream);                                           \
+    /* lago_interp_bspline: the cubic B-spline with coefficients C evaluated at i + dt u(i) for every voxel i.       \
+     * C: (broadcast_C ? 1 : nn, nc, sp)  u: (nn, dim, sp)  out: (nn, nc, sp).  Per axis with extent n: the position \
+     * (lago_interp_forward's expression) is clamped to [0, n - 1] first, f = min(floor(x), n - 2), t = x - f, the   \
+     * taps f - 1 ... f + 2 weigh ((1-t)^3, 3t^3 - 6t^2 + 4, -3t^3 + 3t^2 + 3t + 1, t^3) / 6 and are folded once     \
+     * into the grid (k -> |k|, then k -> 2 (n - 1) - k if k > n - 1; n = 1: index 0): csrc/bspline_weights.hpp.     \
+     * 4^dim taps per voxel and channel (64 gathered elements for dim 3), 4 (dim + 2 nc) streamed bytes per voxel    \
+     * (float32), summed z innermost, then y, then x: the same bits from call to call.  A position outside the grid  \
+     * gives the value at the nearest point of the grid's box, a NaN coordinate gives NaN for that voxel, and no     \
+     * position addresses outside C.  LAGO_ERR_INVALID before any device call: dim not 2 or 3, a negative extent, a  \
+     * plane of 2^29 elements or more, out overlapping an input, a null pointer.  nn, nc or an extent equal to 0:    \
+     * nothing is done (LAGO_OK).  No counterpart in the reference. */                                               \
+    int lago_interp_bspline##SUF(REAL *out, const REAL *C, const REAL *u, double dt, int dim, int64_t nn, int64_t nc, \
+                                 int64_t nx, int64_t ny, int64_t nz, int broadcast_C, void *stream);                 \
+    /* its gradients for an upstream grad_out (nn, nc, sp).  Either output may be NULL when it is not needed         \
+     * (need_C / need_u 0): it is then neither computed nor written.                                                 \
+     *   d_u (nn, dim, sp): d_u[n,a,i] = dt sum_c grad_out[n,c,i] dS_c/dx_a with the derivative weights              \
+     *     (-(1-t)^2, 3t^2 - 4t, -3t^2 + 2t + 1, t^2) / 2 along a; exactly 0 along an axis on which the position     \
+     *     was clamped (continuous there: the mirror makes the derivative vanish at both borders); NaN in every      \
+     *     component for a voxel with a NaN coordinate.  Plain stores: the same bits from call to call.              \
+     *   d_C like C (summed over the items when broadcast_C): zeroed on the stream, then every voxel adds w g to     \
+     *     its 4^dim folded taps, w = (w_x w_y) w_z in REAL (w_y w_z for dim 2), the product w g rounded once; a     \
+     *     voxel with a NaN coordinate adds nothing.  The adds are hardware float atomics on memory: the LAST BITS   \
+     *     of d_C depend on their arrival order and differ from call to call, as lago_interp_backward's d_I.  Cells  \
+     *     that receive nothing hold exactly 0.                                                                      \
+     * An output may not overlap an input or the other output.  No counterpart in the reference. */                  \
+    int lago_interp_bspline_backward##SUF(REAL *d_C, REAL *d_u, const REAL *grad_out, const REAL *C, const REAL *u,   \
+                                          double dt, int dim, int64_t nn, int64_t nc, int64_t nx, int64_t ny,        \
+                                          int64_t nz, int broadcast_C, int need_C, int need_u, void *stream);
 
 LAGO_DECLARE(float, _f32)
 LAGO_DECLARE(double, _f64)

@@ -14,6 +14,8 @@ if not _BUILDING:
     from .affine import (AffineInterp, AffineInterpFunction, RegridFunction, RegridModule, StandardizedDataset,  # noqa: F401
                          affine_atlas, affine_interp, batch_average, load_affine_atlas, save_affine_atlas,
                          affine_inverse, det_2x2, invert_2x2, invert_3x3, regrid, rigid_inverse, rotation_exp_map)
+    from .bspline import (BsplinePrefilterFunction, InterpBsplineFunction, bspline_prefilter, interp_bspline,  # noqa: F401
+                          interp_cubic)
     from .deform import (InterpFunction, InvertDisplacementFunction, compose, compose_disp_vel,  # noqa: F401
                          compose_vel_disp, identity, interp, interp_hessian_diagonal_image, invert_displacement)
     from .diff import (JacobianDeterminantFunction, JacobianTimesVectorFieldAdjointFunction,  # noqa: F401

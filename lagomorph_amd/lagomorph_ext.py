@@ -84,6 +84,9 @@ _SIGS = {
     "lago_warp_labels": [_vp, _vp, _vp, _dbl, _int, _int, _int, _i64, _i64, _i64, _i64, _vp],
     "lago_interp_points": [_vp, _vp, _vp, _int, _i64, _i64, _i64, _i64, _i64, _i64, _int, _vp],
     "lago_interp_points_backward": [_vp, _vp, _vp, _vp, _vp, _int, _i64, _i64, _i64, _i64, _i64, _i64, _int, _int, _int, _vp],
+    "lago_bspline_prefilter": [_vp, _vp, _int, _int, _i64, _i64, _i64, _i64, _vp],
+    "lago_interp_bspline": [_vp, _vp, _vp, _dbl, _int, _i64, _i64, _i64, _i64, _i64, _int, _vp],
+    "lago_interp_bspline_backward": [_vp, _vp, _vp, _vp, _vp, _dbl, _int, _i64, _i64, _i64, _i64, _i64, _int, _int, _int, _vp],
     "lago_fluid_metric": [_vp, _vp, _vp, _i64, _int, _vp, _vp, _vp, _vp, _vp, _vp, _dbl, _dbl, _dbl, _int, _i64, _i64,
                           _i64, _i64, _vp],
     "lago_fluid_metric_scaled": [_vp, _vp, _vp, _i64, _int, _vp, _vp, _vp, _vp, _vp, _vp, _dbl, _dbl, _dbl, _int, _i64,
@@ -927,6 +930,90 @@ def interp_points_backward(grad_out, F, x, need_F, need_x):
         _call("lago_interp_points_backward", F, _ptr(d_F), _ptr(d_x), _ptr(grad_out), _ptr(F), _ptr(x), dim, nn,
               F.size(1), x.size(2), nx, ny, nz, int(bc), int(bool(need_F)), int(bool(need_x)))
     return [d_F, d_x]
+
+
+def _check_types(named):
+    """Every (name, tensor) pair is a tensor of one supported floating dtype, the first one's."""
+    for name, t in named:
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"{name} must be a torch.Tensor")
+    for name, t in named:
+        _suffix(t)
+    for name, t in named[1:]:
+        if t.dtype != named[0][1].dtype:
+            raise RuntimeError(f"lagomorph_ext: dtype mismatch ({named[0][1].dtype} vs {t.dtype})")
+
+
+def _check_layout(named):
+    """Contiguity, then -- last, so that every other error is raised whatever device the tensors are on -- the devices."""
+    for name, t in named:
+        if not t.is_contiguous():
+            raise RuntimeError(f"{name} must be contiguous")
+    for name, t in named[1:]:
+        if t.device != named[0][1].device:
+            raise RuntimeError(f"lagomorph_ext: device mismatch ({named[0][1].device} vs {t.device})")
+    for name, t in named:
+        _check_input(t, name)
+
+
+def bspline_prefilter(I, adjoint=False):
+    """Cubic B-spline coefficients (N, C, *sp) of the samples I (N, C, *sp), mirror border; adjoint: the transposed
+    operator.  lago_bspline_prefilter of include/lagomorph_hip.h (csrc/bspline.hip).  Not in the reference; no CPU path."""
+    _check_types((("I", I),))
+    dim, nx, ny, nz = _spatial(I)
+    if dim not in (2, 3):
+        raise RuntimeError(f"bspline_prefilter: I must be a field of shape (N, C, *spatial) with two or three spatial axes, "
+                           f"got shape {tuple(I.shape)}")
+    _check_layout((("I", I),))
+    out = torch.empty_like(I)
+    _call("lago_bspline_prefilter", I, _ptr(out), _ptr(I), int(bool(adjoint)), dim, I.size(0) * I.size(1), nx, ny, nz)
+    return out
+
+
+def _check_bspline(C, u, what, grad_out=None):
+    """Coefficients C (N or 1, K, *sp) with two or three spatial axes and a displacement u (N, d, *sp) of one floating
+    dtype (and, for the backward, grad_out (N, K, *sp)); returns (dim, nn, broadcast).  Every error of type, dtype,
+    shape, batch and contiguity is raised whatever device the tensors are on; the device checks come last."""
+    named = (("C", C), ("u", u)) + ((("grad_out", grad_out),) if grad_out is not None else ())
+    _check_types(named)
+    dim = C.dim() - 2
+    if dim not in (2, 3):
+        raise RuntimeError(f"{what}: C must be a field of shape (N, K, *spatial) with two or three spatial axes, "
+                           f"got shape {tuple(C.shape)}")
+    if u.dim() != C.dim() or u.size(1) != dim or tuple(u.shape[2:]) != tuple(C.shape[2:]):
+        raise RuntimeError(f"{what}: displacement of shape {tuple(u.shape)} does not match the field {tuple(C.shape)}")
+    nn = u.size(0)
+    if C.size(0) not in (1, nn):
+        raise RuntimeError(f"{what}: batch sizes of C ({C.size(0)}) and u ({nn}) are incompatible")
+    if grad_out is not None and tuple(grad_out.shape) != (nn, C.size(1)) + tuple(C.shape[2:]):
+        raise RuntimeError(f"{what}: grad_out of shape {tuple(grad_out.shape)} does not match the output "
+                           f"{(nn, C.size(1)) + tuple(C.shape[2:])}")
+    _check_layout(named)
+    return dim, nn, C.size(0) < nn
+
+
+def interp_bspline_forward(C, u, dt=1.0):
+    """out (N, K, *sp): the cubic B-spline with coefficients C (N or 1, K, *sp) at i + dt u(i); lago_interp_bspline
+    (csrc/bspline.hip: interp_bspline_fwd_kernel).  Not in the reference; no CPU path."""
+    dim, nn, bc = _check_bspline(C, u, "interp_bspline")
+    _, nx, ny, nz = _spatial(C)
+    out = torch.empty((nn, C.size(1)) + tuple(C.shape[2:]), dtype=C.dtype, device=C.device)
+    _call("lago_interp_bspline", C, _ptr(out), _ptr(C), _ptr(u), float(dt), dim, nn, C.size(1), nx, ny, nz, int(bc))
+    return out
+
+
+def interp_bspline_backward(grad_out, C, u, dt, need_C, need_u):
+    """[d_C like C or None, d_u like u or None] for grad_out (N, K, *sp): lago_interp_bspline_backward
+    (csrc/bspline.hip: interp_bspline_bwd_kernel).  A gradient that is not needed is not computed.  d_C is a sum of
+    hardware float atomics (its last bits differ from call to call), d_u repeats bit for bit."""
+    dim, nn, bc = _check_bspline(C, u, "interp_bspline_backward", grad_out)
+    _, nx, ny, nz = _spatial(C)
+    d_C = torch.empty_like(C) if need_C else None
+    d_u = torch.empty_like(u) if need_u else None
+    if need_C or need_u:
+        _call("lago_interp_bspline_backward", C, _ptr(d_C), _ptr(d_u), _ptr(grad_out), _ptr(C), _ptr(u), float(dt), dim, nn,
+              C.size(1), nx, ny, nz, int(bc), int(bool(need_C)), int(bool(need_u)))
+    return [d_C, d_u]
 
 
 def fluid_operator(Fmv, inverse, cosluts, sinluts, alpha, beta, gamma):
