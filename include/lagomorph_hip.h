@@ -469,10 +469,43 @@ long long lago_reversed_launches(void);
      * An output may not overlap an input or the other output.  No counterpart in the reference. */                  \
     int lago_interp_bspline_backward##SUF(REAL *d_C, REAL *d_u, const REAL *grad_out, const REAL *C, const REAL *u,   \
                                           double dt, int dim, int64_t nn, int64_t nc, int64_t nx, int64_t ny,        \
-                                          int64_t nz, int broadcast_C, int need_C, int need_u, void *stream);
+                                          int64_t nz, int broadcast_C, int need_C, int need_u, void *stream);       \
+    /* lago_ffd_expand: a free-form deformation's control lattice expanded to a dense field by its uniform cubic     \
+     * B-spline.  ctrl: (rows, mx, my[, mz])  out: (rows, nx, ny[, nz]), rows = batch items times channels, sx, sy   \
+     * [, sz] the integer control spacing per axis in voxels, each in 1..32 (dim 2: nz and sz are ignored).  Per     \
+     * axis with extent n and spacing s: m = (n - 1) / s + 4 control points, point j at voxel (j - 1) s; voxel x has \
+     * the taps i ... i + 3, i = x / s, weighed ((1-t)^3, 3t^3 - 6t^2 + 4, -3t^3 + 3t^2 + 3t + 1, t^3) / 6 at        \
+     * t = (REAL)(x % s) / (REAL)s (csrc/ffd_weights.hpp: the expressions of bspline_weights.hpp, no fma); every tap \
+     * is inside the lattice, nothing is folded or clamped.  out[r,x,y,z] = sum_c Wz[z,c] (sum_b Wy[y,b] (sum_a      \
+     * Wx[x,a] ctrl[r,a,b,c])): the axes contracted one after the other in LDS, x first, each 4-tap sum as the tap-0  \
+     * product and one fma per further tap, ascending.  4 bytes stored per element (float32), the lattice read from  \
+     * cache; no atomics: the same bits from call to call.  LAGO_ERR_INVALID before any device call: dim not 2 or 3, \
+     * a negative extent, a spacing outside 1..32, a plane of 2^29 elements or more, a null pointer, out overlapping \
+     * ctrl.  rows or an extent equal to 0: nothing is done (LAGO_OK).  No counterpart in the reference. */          \
+    int lago_ffd_expand##SUF(REAL *out, const REAL *ctrl, int dim, int64_t rows, int64_t nx, int64_t ny, int64_t nz, \
+                             int sx, int sy, int sz, void *stream);                                                  \
+    /* its adjoint: d_ctrl[r,a,b,c] = sum_{x,y,z} Wx[x,a] Wy[y,b] Wz[z,c] grad_out[r,x,y,z], the same weights.       \
+     * grad_out: (rows, nx, ny[, nz])  d_ctrl: (rows, mx, my[, mz]).  Workgroups own voxel tiles of 8 x 8 x 64       \
+     * (dim 2: 64 x 64), read them once and reduce them in LDS, z first, then y, then x: per control point the taps  \
+     * q = 0..3 in order, the voxels of a cell ascending, acc = fma(w, v, acc) from 0.  The partial sums of a tile   \
+     * go to `scratch` with plain stores (lago_ffd_scratch_elems elements of REAL, need not be initialised,          \
+     * clobbered) and a second kernel adds, per control point, the partials of the tiles that reach it, tiles        \
+     * ascending.  4 bytes loaded per element (float32) plus the partials; no atomic on memory: the same bits from   \
+     * call to call, and a control point that no voxel reaches, or only with weight 0, holds exactly 0.              \
+     * LAGO_ERR_INVALID before any device call: as lago_ffd_expand, and scratch_elems too small, d_ctrl overlapping  \
+     * grad_out or scratch, scratch overlapping grad_out.  rows or an extent equal to 0: nothing is done (LAGO_OK;   \
+     * d_ctrl is not written).  No counterpart in the reference. */                                                  \
+    int lago_ffd_expand_adjoint##SUF(REAL *d_ctrl, const REAL *grad_out, REAL *scratch, int64_t scratch_elems,       \
+                                     int dim, int64_t rows, int64_t nx, int64_t ny, int64_t nz, int sx, int sy,      \
+                                     int sz, void *stream);
 
 LAGO_DECLARE(float, _f32)
 LAGO_DECLARE(double, _f64)
+
+/* Elements of REAL that lago_ffd_expand_adjoint needs as scratch for this problem (the partial sums of every voxel
+ * tile: rows x tiles x the control points a tile reaches); 0 for an empty problem, -1 for arguments the entry point
+ * rejects.  The caller allocates.  No counterpart in the reference. */
+long long lago_ffd_scratch_elems(int dim, int64_t rows, int64_t nx, int64_t ny, int64_t nz, int sx, int sy, int sz);
 
 /* How many scratch tables per row lago_mi_histogram can use for `rows` rows of `nvox` voxels at `bins` bins (>= 1: a
  * row is cut into chunks of a few thousand voxels, as many as keep the scratch of all rows within 8 MB).  The caller

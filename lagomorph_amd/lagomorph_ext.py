@@ -87,6 +87,8 @@ _SIGS = {
     "lago_bspline_prefilter": [_vp, _vp, _int, _int, _i64, _i64, _i64, _i64, _vp],
     "lago_interp_bspline": [_vp, _vp, _vp, _dbl, _int, _i64, _i64, _i64, _i64, _i64, _int, _vp],
     "lago_interp_bspline_backward": [_vp, _vp, _vp, _vp, _vp, _dbl, _int, _i64, _i64, _i64, _i64, _i64, _int, _int, _int, _vp],
+    "lago_ffd_expand": [_vp, _vp, _int, _i64, _i64, _i64, _i64, _int, _int, _int, _vp],
+    "lago_ffd_expand_adjoint": [_vp, _vp, _vp, _i64, _int, _i64, _i64, _i64, _i64, _int, _int, _int, _vp],
     "lago_fluid_metric": [_vp, _vp, _vp, _i64, _int, _vp, _vp, _vp, _vp, _vp, _vp, _dbl, _dbl, _dbl, _int, _i64, _i64,
                           _i64, _i64, _vp],
     "lago_fluid_metric_scaled": [_vp, _vp, _vp, _i64, _int, _vp, _vp, _vp, _vp, _vp, _vp, _dbl, _dbl, _dbl, _int, _i64,
@@ -108,6 +110,8 @@ _lib.lago_label_overlap.argtypes = [_vp, _vp, _vp, _vp, _i64, _int, _i64, _i64, 
 _lib.lago_label_overlap.restype = _int
 _lib.lago_label_overlap_scratch_chunks.argtypes = [_int, _i64, _i64]
 _lib.lago_label_overlap_scratch_chunks.restype = _int
+_lib.lago_ffd_scratch_elems.argtypes = [_int, _i64, _i64, _i64, _i64, _int, _int, _int]
+_lib.lago_ffd_scratch_elems.restype = ctypes.c_longlong
 
 
 class LagoTuning(ctypes.Structure):
@@ -1014,6 +1018,97 @@ def interp_bspline_backward(grad_out, C, u, dt, need_C, need_u):
         _call("lago_interp_bspline_backward", C, _ptr(d_C), _ptr(d_u), _ptr(grad_out), _ptr(C), _ptr(u), float(dt), dim, nn,
               C.size(1), nx, ny, nz, int(bc), int(bool(need_C)), int(bool(need_u)))
     return [d_C, d_u]
+
+
+FFD_MAX_SPACING = 32   # spacings lago_ffd_expand takes: 1..32 voxels
+
+
+def ffd_spacing(spacing, dim):
+    """`spacing` as a tuple of `dim` integers: one integer for every axis, or one per axis.  RuntimeError otherwise."""
+    sp = (spacing,) * dim if isinstance(spacing, int) and not isinstance(spacing, bool) else spacing
+    try:
+        sp = tuple(sp)
+        ok = len(sp) == dim and all(isinstance(v, int) and not isinstance(v, bool) and 1 <= v <= FFD_MAX_SPACING for v in sp)
+    except TypeError:
+        ok = False
+    if not ok:
+        raise RuntimeError(f"ffd: spacing must be one integer in 1..{FFD_MAX_SPACING}, or one per spatial axis ({dim}), "
+                           f"got {spacing!r}")
+    return sp
+
+
+def ffd_grid_shape(shape, spacing):
+    """Control-lattice extents for a field of spatial `shape` (two or three extents >= 1): (n - 1) // s + 4 per axis."""
+    try:
+        shape = tuple(shape)
+        ok = len(shape) in (2, 3) and all(isinstance(n, int) and not isinstance(n, bool) and n >= 1 for n in shape)
+    except TypeError:
+        ok = False
+    if not ok:
+        raise RuntimeError(f"ffd: shape must give two or three spatial axes with extents >= 1, got {shape!r}")
+    return tuple((n - 1) // s + 4 for n, s in zip(shape, ffd_spacing(spacing, len(shape))))
+
+
+def _check_ffd(x, shape, spacing, what):
+    """A control lattice x (N, C, *m) with the field's spatial `shape` (forward), or a field x (N, C, *sp) with shape
+    None (adjoint); returns (dim, field shape, spacing tuple).  Every error of type, dtype, shape and contiguity is
+    raised whatever device the tensor is on; the device checks come last."""
+    name = "ctrl" if shape is not None else "g"
+    _check_types(((name, x),))
+    dim = x.dim() - 2
+    if dim not in (2, 3):
+        raise RuntimeError(f"{what}: {name} must be a field of shape (N, C, *spatial) with two or three spatial axes, "
+                           f"got shape {tuple(x.shape)}")
+    if shape is None:
+        shape = tuple(x.shape[2:])
+        if min(shape) < 1:
+            raise RuntimeError(f"{what}: g of shape {tuple(x.shape)} has an empty spatial axis")
+    else:
+        try:
+            shape = tuple(shape)
+        except TypeError:
+            raise RuntimeError(f"ffd: shape must give two or three spatial axes with extents >= 1, got {shape!r}") from None
+        if len(shape) != dim:
+            raise RuntimeError(f"{what}: a control grid of shape {tuple(x.shape)} does not match a field with "
+                               f"{len(shape)} spatial axes ({shape})")
+    sp = ffd_spacing(spacing, dim)
+    if name == "ctrl" and tuple(x.shape[2:]) != ffd_grid_shape(shape, sp):
+        raise RuntimeError(f"{what}: a control grid of shape {tuple(x.shape)} does not match the field {shape} at spacing "
+                           f"{sp}: its spatial extents must be {ffd_grid_shape(shape, sp)}")
+    _check_layout(((name, x),))
+    return dim, shape, sp
+
+
+def _ffd_args(dim, shape, sp):
+    return (dim,), tuple(shape) + (1,) * (3 - dim), tuple(sp) + (1,) * (3 - dim)
+
+
+def ffd_expand(ctrl, shape, spacing):
+    """out (N, C, *shape): the control lattice ctrl (N, C, *ffd_grid_shape(shape, spacing)) expanded by its uniform
+    cubic B-spline; lago_ffd_expand of include/lagomorph_hip.h (csrc/ffd.hip: ffd_expand_kernel).  No atomics: the
+    same bits from call to call.  Not in the reference; no CPU path."""
+    dim, shape, sp = _check_ffd(ctrl, shape, spacing, "ffd_expand")
+    out = torch.empty(tuple(ctrl.shape[:2]) + shape, dtype=ctrl.dtype, device=ctrl.device)
+    (d,), n, s = _ffd_args(dim, shape, sp)
+    _call("lago_ffd_expand", ctrl, _ptr(out), _ptr(ctrl), d, ctrl.size(0) * ctrl.size(1), *n, *s)
+    return out
+
+
+def ffd_expand_adjoint(g, spacing):
+    """d_ctrl (N, C, *ffd_grid_shape(g.shape[2:], spacing)) for g (N, C, *sp): the transpose of ffd_expand;
+    lago_ffd_expand_adjoint (csrc/ffd.hip: ffd_restrict_tile_kernel, ffd_restrict_sum_kernel).  The scratch of
+    per-tile partial sums is allocated here.  No atomic on memory: the same bits from call to call, and control points
+    that no voxel reaches hold exactly 0."""
+    dim, shape, sp = _check_ffd(g, None, spacing, "ffd_expand_adjoint")
+    rows = g.size(0) * g.size(1)
+    d_ctrl = torch.empty(tuple(g.shape[:2]) + ffd_grid_shape(shape, sp), dtype=g.dtype, device=g.device)
+    (d,), n, s = _ffd_args(dim, shape, sp)
+    elems = int(_lib.lago_ffd_scratch_elems(d, rows, *n, *s))
+    if elems < 0:
+        raise RuntimeError(_lib.lago_last_error().decode("utf-8", "replace"))
+    scratch = torch.empty((elems,), dtype=g.dtype, device=g.device)
+    _call("lago_ffd_expand_adjoint", g, _ptr(d_ctrl), _ptr(g), _ptr(scratch), elems, d, rows, *n, *s)
+    return d_ctrl
 
 
 def fluid_operator(Fmv, inverse, cosluts, sinluts, alpha, beta, gamma):
