@@ -55,6 +55,13 @@ extern "C" {
 #define LAGO_LABELS_VOTE 1
 #define LAGO_LABELS_MAX 4096
 
+/* lago_distance_transform: which voxels of the label map are features, and the largest extent an axis may have */
+#define LAGO_EDT_NONZERO 0
+#define LAGO_EDT_EQUAL 1
+#define LAGO_EDT_NOT_EQUAL 2
+#define LAGO_EDT_SURFACE 3
+#define LAGO_EDT_MAX_EXTENT 1024
+
 /* ---- housekeeping --------------------------------------------------------- */
 
 /* replaces set_debug_mode (extension.cpp:105-107): when non-zero every entry
@@ -524,6 +531,27 @@ int lago_mi_scratch_tables(int bins, int64_t rows, int64_t nvox);
 int lago_label_overlap(long long *counts, const int32_t *A, const int32_t *B, uint32_t *scratch, int64_t scratch_chunks,
                        int num_labels, int64_t rows, int64_t nvox, void *stream);
 int lago_label_overlap_scratch_chunks(int num_labels, int64_t rows, int64_t nvox);
+
+/* distance_transform: out[n, x] = the Euclidean distance (squared != 0: its square) from voxel x to the nearest FEATURE
+ * voxel of item n, 0 on features, +inf everywhere in an item without one.  L: (nn, 1, sp) int32 label values, out:
+ * (nn, 1, sp) float32.  The features (`where`):
+ *   LAGO_EDT_NONZERO    L != 0
+ *   LAGO_EDT_EQUAL      L == label
+ *   LAGO_EDT_NOT_EQUAL  L != label
+ *   LAGO_EDT_SURFACE    L == label and one of the 2 dim face neighbours != label, a neighbour outside the volume counting
+ *                       as different (the mask minus its erosion by the face-connected cross, border value 0)
+ * spacing: `dim` doubles ON THE HOST, one per spatial axis in order, each narrowed to float32 and positive and finite
+ * there.  The squared distance is sum_a (s_a delta_a)^2.  One pass per axis, the last (contiguous) axis first, each per
+ * line  out[i] = min_j g[j] + t t, t = s float(i - j)  in float32 with nothing fused (csrc/edt_line.hpp); the first pass
+ * forms g (0 on a feature, +inf elsewhere) from L as it loads, the later ones run in place on out, the last takes the
+ * correctly rounded square root unless `squared`.  With every spacing 1 all values are integers below 2^24, so the
+ * squared distance is exact; otherwise it is within 8 * 2^-24 relative of the real value (no term is negative).  No
+ * atomic, no scratch buffer: the same bits from call to call.
+ * LAGO_ERR_INVALID before any device call: dim not 2 or 3, an unknown `where`, a spacing that is not positive, a negative
+ * extent or one above LAGO_EDT_MAX_EXTENT, 2^31 voxels or more in all, a null pointer, out overlapping L.  nn or an
+ * extent equal to 0: nothing is done (LAGO_OK).  No counterpart in the reference. */
+int lago_distance_transform(float *out, const int32_t *L, int where, int32_t label, const double *spacing, int squared,
+                            int dim, int64_t nn, int64_t nx, int64_t ny, int64_t nz, void *stream);
 
 /* ---- fused geometry operators (beyond the reference's extension surface) -------------
  * compose: out = ds*u + dt*interp(v, u, ds) in one pass -- deform.compose

@@ -21,6 +21,7 @@ if not _BUILDING:
     from .diff import (JacobianDeterminantFunction, JacobianTimesVectorFieldAdjointFunction,  # noqa: F401
                        JacobianTimesVectorFieldFunction, jacobian_determinant, jacobian_times_vectorfield,
                        jacobian_times_vectorfield_adjoint)
+    from .distance import distance_transform, signed_distance, surface_distance, surface_mask  # noqa: F401
     from .ffd import FFDFunction, ffd_expand, ffd_grid_shape, ffd_restrict  # noqa: F401
     from .labels import dice, label_overlap, warp_labels  # noqa: F401
     from .lagomorph_ext import set_debug_mode  # noqa: F401

@@ -110,6 +110,8 @@ _lib.lago_label_overlap.argtypes = [_vp, _vp, _vp, _vp, _i64, _int, _i64, _i64, 
 _lib.lago_label_overlap.restype = _int
 _lib.lago_label_overlap_scratch_chunks.argtypes = [_int, _i64, _i64]
 _lib.lago_label_overlap_scratch_chunks.restype = _int
+_lib.lago_distance_transform.argtypes = [_vp, _vp, _int, ctypes.c_int32, ctypes.POINTER(_dbl), _int, _int, _i64, _i64, _i64, _i64, _vp]
+_lib.lago_distance_transform.restype = _int
 _lib.lago_ffd_scratch_elems.argtypes = [_int, _i64, _i64, _i64, _i64, _int, _int, _int]
 _lib.lago_ffd_scratch_elems.restype = ctypes.c_longlong
 
@@ -872,6 +874,61 @@ def label_overlap(A, B, num_labels):
     scratch = torch.empty((rows * chunks * K * 3,), dtype=torch.int32, device=A.device)
     _launch(_lib.lago_label_overlap, A, _ptr(counts), _ptr(A32), _ptr(B32), _ptr(scratch), chunks, K, rows, nvox)
     return counts
+
+
+EDT_WHERE = {"nonzero": 0, "equal": 1, "not_equal": 2, "surface": 3}   # LAGO_EDT_* of include/lagomorph_hip.h
+EDT_MAX_EXTENT = 1024                                                  # LAGO_EDT_MAX_EXTENT
+
+
+def edt_where(where):
+    if not isinstance(where, str) or where not in EDT_WHERE:
+        raise ValueError(f"distance_transform: where must be one of {sorted(EDT_WHERE)} (got {where!r})")
+    return EDT_WHERE[where]
+
+
+def edt_spacing(spacing, dim):
+    """One positive float, or one per spatial axis, as a tuple of `dim` floats that are positive and finite in float32
+    (what the kernels compute in)."""
+    try:
+        sp = (float(spacing),) * dim if not hasattr(spacing, "__len__") else tuple(float(s) for s in spacing)
+    except (TypeError, ValueError):
+        raise ValueError(f"distance_transform: spacing must be a positive float or one per axis (got {spacing!r})") from None
+    if len(sp) != dim:
+        raise ValueError(f"distance_transform: spacing must have one entry per spatial axis ({dim}), got {len(sp)}")
+    for s in sp:
+        if not (s > 0.0 and math.isfinite(s) and 1e-38 < s < 3e38):
+            raise ValueError(f"distance_transform: spacing must be positive and finite in float32 (got {spacing!r})")
+    return sp
+
+
+def distance_transform(L, where="nonzero", label=0, spacing=1.0, squared=False):
+    """float32 (N, 1, *sp): the Euclidean distance (squared=True: its square) from every voxel to the nearest feature
+    voxel of its item; L (N, 1, *sp) integer or bool labels, features by `where` ("nonzero", "equal", "not_equal",
+    "surface" of `label`); the definition is in include/lagomorph_hip.h (csrc/edt.hip: edt_pass_kernel, one launch per
+    axis, no scratch buffer).  The call takes int32 (see warp_labels).  Not in the reference; no CPU path."""
+    where = edt_where(where)
+    if not isinstance(L, torch.Tensor):
+        raise TypeError("L must be a torch.Tensor")
+    if L.dtype != torch.bool:
+        _check_labels(L, "L")
+    elif L.dim() not in (4, 5) or L.size(1) != 1:
+        raise RuntimeError(f"L must be a label map of shape (N, 1, *spatial) with two or three spatial axes, got shape {tuple(L.shape)}")
+    try:
+        ok = not isinstance(label, bool) and int(label) == label and -2**31 <= int(label) < 2**31
+    except (TypeError, ValueError):
+        ok = False
+    if not ok:
+        raise ValueError(f"distance_transform: label must be an integer in the int32 range (got {label!r})")
+    dim, nx, ny, nz = _spatial(L)
+    sp = edt_spacing(spacing, dim)
+    if max(L.shape[2:]) > EDT_MAX_EXTENT:
+        raise RuntimeError(f"distance_transform: extents up to {EDT_MAX_EXTENT} are supported, got shape {tuple(L.shape)}")
+    _check_input(L, "L")
+    L32 = _as_int32(L)
+    out = torch.empty(L.shape, dtype=torch.float32, device=L.device)
+    _launch(_lib.lago_distance_transform, L, _ptr(out), _ptr(L32), where, int(label), (_dbl * dim)(*sp), int(bool(squared)), dim,
+            L.size(0), nx, ny, nz)
+    return out
 
 
 def _check_points(F, x, what, grad_out=None, backward=False):
