@@ -37,6 +37,9 @@ extern "C" {
 #define LAGO_ERR_INVALID (-1)
 #define LAGO_ERR_HIP (-2)
 
+/* (version 5 as before: no signature changed when extents whose product nx*ny*nz does not fit int64_t became
+ * LAGO_ERR_INVALID in every entry point -- they used to wrap, and some wrapped values were accepted.  No tensor has
+ * such a shape.) */
 #define LAGO_ABI_VERSION 5
 
 /* lago_gauss_smooth: the largest radius (taps on each side of the centre) a pass takes, and the border modes */

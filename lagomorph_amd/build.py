@@ -38,7 +38,8 @@ FLAGS = [
 
 
 def _deps():
-    return [os.path.join(CSRC, h) for h in ("common.hpp", "launch.hpp", "gauss.hpp", "fft_lds.hpp", "fft3_sizes.hpp", "stencil_tile.hpp", "gather_window.hpp", "splat_window.hpp", "fluid_bin.hpp", "affine_box.hpp", "mi_window.hpp", "label_vote.hpp", "edt_line.hpp", "bspline_weights.hpp", "ffd_weights.hpp")] + [
+    """Every header an object may include: a change to any of them rebuilds every object."""
+    return sorted(os.path.join(CSRC, h) for h in os.listdir(CSRC) if h.endswith(".hpp")) + [
         os.path.join(HERE, "..", "include", "lagomorph_hip.h")]
 
 

@@ -31,8 +31,6 @@
 // then x), so forward and d_u repeat bit for bit; d_C is a scatter of w g onto the 4^d folded taps with hardware float
 // atomics onto a target the entry point zeroes on the stream: its last bits vary from call to call.  No tap index
 // leaves [0, n - 1] for any position, finite or not.  Registers, LDS and occupancy are in DESIGN.md.
-#include <limits.h>
-
 #include "common.hpp"
 #include "bspline_weights.hpp"
 
@@ -168,25 +166,16 @@ static int bs_tile_lines(int n) {
 template <typename R>
 static int bspline_prefilter_impl(R *out, const R *in, int adjoint, int dim, int64_t rows, int64_t nx, int64_t ny, int64_t nz,
                                   void *stream) {
-    if (dim != 2 && dim != 3)
-        return fail_invalid("bspline_prefilter: Only two- and three-dimensional fields are supported (dim %d)", dim);
-    if (dim == 2) {   // (ny, nz) = (H, W), as Geom
-        nz = ny;
-        ny = nx;
-        nx = 1;
-    }
-    if (rows < 0 || nx < 0 || ny < 0 || nz < 0) return fail_invalid("bspline_prefilter: negative extent");
-    if (nx > INT_MAX || ny > INT_MAX || nz > INT_MAX) return fail_invalid("bspline_prefilter: an extent of 2^31 or more");
-    const int64_t nxy = nx * ny;   // < 2^62; nvox * 8 < 2^32: one plane is addressed with 32-bit offsets
-    if (nxy >= (1ll << 29) || nxy * nz >= (1ll << 29)) return fail_invalid("bspline_prefilter: a channel plane of 2^29 elements or more");
-    const int64_t nvox = nxy * nz;
+    Volume v;   // nvox * 8 < 2^32: one plane is addressed with 32-bit offsets
+    if (const int rc = check_volume(v, "bspline_prefilter", dim, nx, ny, nz, kPlane29, {rows})) return rc;
+    const int64_t nvox = v.nvox;
     if (rows == 0 || nvox == 0) return LAGO_OK;   // nothing to write
     if (rows >= (1ll << 31)) return fail_invalid("bspline_prefilter: 2^31 rows or more");
     if (!out || !in) return fail_invalid("bspline_prefilter: null pointer");
     const size_t bytes = (size_t)rows * (size_t)nvox * sizeof(R);
     if (overlaps(out, in, bytes)) return fail_invalid("bspline_prefilter: out must not overlap the input");
     // the launches' grids, before the first of them
-    const int64_t ext[3] = {nx, ny, nz}, inner_of[3] = {ny * nz, nz, 1};
+    const int64_t ext[3] = {v.nx, v.ny, v.nz}, inner_of[3] = {v.ny * v.nz, v.nz, 1};
     for (int a = 0; a < 3; ++a) {
         if (ext[a] <= 1) continue;
         const int64_t lines = nvox / ext[a];
@@ -406,18 +395,12 @@ static std::atomic<int> g_bs_dbg_gather{1};
 #endif
 
 // The checks the two gather entry points share, before any device call.  LAGO_OK with `empty` set: nothing to do.
-static int bspline_geom(const char *what, Geom &g, bool &empty, int dim, int64_t nn, int64_t nc, int64_t nx, int64_t ny,
-                        int64_t nz, bool scatter) {
-    if (dim != 2 && dim != 3) return fail_invalid("%s: Only two- and three-dimensional fields are supported (dim %d)", what, dim);
-    if (dim == 2) nz = 1;
-    if (nn < 0 || nc < 0 || nx < 0 || ny < 0 || nz < 0) return fail_invalid("%s: negative extent", what);
-    if (nx > INT_MAX || ny > INT_MAX || nz > INT_MAX) return fail_invalid("%s: an extent of 2^31 or more", what);
+static int bspline_geom(const char *what, Geom &g, Volume &v, bool &empty, int dim, int64_t nn, int64_t nc, int64_t nx,
+                        int64_t ny, int64_t nz, bool scatter) {
+    if (const int rc = check_volume(v, what, dim, nx, ny, nz, kPlane29, {nn, nc})) return rc;
     if (nc > INT_MAX) return fail_invalid("%s: 2^31 channels or more", what);
-    const int64_t nxy = nx * ny;
-    if (nxy >= (1ll << 29) || nxy * nz >= (1ll << 29)) return fail_invalid("%s: a channel plane of 2^29 elements or more", what);
-    empty = nn == 0 || nc == 0 || nxy * nz == 0;
-    if (empty) return LAGO_OK;
-    if (!make_geom(g, dim, nn, nx, ny, dim == 2 ? 1 : nz, kBlock, scatter)) return fail_invalid("%s: bad extent", what);
+    empty = nn == 0 || nc == 0 || v.nvox == 0;
+    if (!empty && !make_geom(g, v, nn, kBlock, scatter)) return fail_invalid("%s: bad extent", what);
     return LAGO_OK;
 }
 
@@ -425,14 +408,12 @@ template <typename R>
 static int interp_bspline_impl(R *out, const R *C, const R *u, double dt, int dim, int64_t nn, int64_t nc, int64_t nx,
                                int64_t ny, int64_t nz, int bc, void *stream) {
     Geom g;
+    Volume v;
     bool empty;
-    if (const int rc = bspline_geom("interp_bspline", g, empty, dim, nn, nc, nx, ny, nz, false)) return rc;
+    if (const int rc = bspline_geom("interp_bspline", g, v, empty, dim, nn, nc, nx, ny, nz, false)) return rc;
     if (empty) return LAGO_OK;   // nothing to write
-    if (!out || !C || !u) return fail_invalid("interp_bspline: null pointer");
-    const size_t obytes = (size_t)nn * nc * g.nvox * sizeof(R), cbytes = (size_t)(bc ? 1 : nn) * nc * g.nvox * sizeof(R),
-                 ubytes = (size_t)nn * dim * g.nvox * sizeof(R);
-    if (overlaps(out, obytes, C, cbytes) || overlaps(out, obytes, u, ubytes))
-        return fail_invalid("interp_bspline: out must not overlap an input");
+    const GatherBytes b(sizeof(R), sizeof(R), dim, nn, nc, v.nvox, v.nvox, bc);
+    if (const int rc = check_gather("interp_bspline", out, C, u, b); rc != kLaunchNow) return rc;
     hipStream_t s = (hipStream_t)stream;
     hipError_t e = hipSuccess;
     with_dim(dim, [&](auto DIM) {
@@ -446,8 +427,7 @@ static int interp_bspline_impl(R *out, const R *C, const R *u, double dt, int di
             e = launch(interp_bspline_fwd_kernel<R, DIM(), BC()>, dim3(g.nblocks), dim3(kBlock), 0, s, out, C, u, dt, (int)nc, g);
         }, bc != 0);
     });
-    if (e != hipSuccess) return fail_hip(e, "interp_bspline");
-    return finish_launch(s, "interp_bspline");
+    return launched(e, s, "interp_bspline");
 }
 
 template <typename R>
@@ -455,37 +435,22 @@ static int interp_bspline_backward_impl(R *d_C, R *d_u, const R *go, const R *C,
                                         int64_t nc, int64_t nx, int64_t ny, int64_t nz, int bc, int need_C, int need_u,
                                         void *stream) {
     Geom g;
+    Volume v;
     bool empty;
-    if (const int rc = bspline_geom("interp_bspline_backward", g, empty, dim, nn, nc, nx, ny, nz, need_C != 0)) return rc;
+    if (const int rc = bspline_geom("interp_bspline_backward", g, v, empty, dim, nn, nc, nx, ny, nz, need_C != 0)) return rc;
     hipStream_t s = (hipStream_t)stream;
-    if (empty) {   // no voxel adds anything: a d_C that has cells is all zeros; a d_u has no element or only empty sums
-        const int64_t nv = (dim == 2 ? nx * ny : nx * ny * nz);
-        const size_t cb = (size_t)(bc ? 1 : nn) * nc * nv * sizeof(R), ub = (size_t)nn * dim * nv * sizeof(R);
-        if (need_C && d_C && cb) LAGO_HIP_TRY(hipMemsetAsync(d_C, 0, cb, s));
-        if (need_u && d_u && ub) LAGO_HIP_TRY(hipMemsetAsync(d_u, 0, ub, s));
-        return LAGO_OK;
-    }
-    if (!need_C && !need_u) return LAGO_OK;
-    if ((need_C && !d_C) || (need_u && (!d_u || !C)) || !go || !u) return fail_invalid("interp_bspline_backward: null pointer");
-    const size_t gbytes = (size_t)nn * nc * g.nvox * sizeof(R), cbytes = (size_t)(bc ? 1 : nn) * nc * g.nvox * sizeof(R),
-                 ubytes = (size_t)nn * dim * g.nvox * sizeof(R);
-    if (need_C && (overlaps(d_C, cbytes, go, gbytes) || overlaps(d_C, cbytes, u, ubytes) || (C && overlaps(d_C, cbytes, C, cbytes))))
-        return fail_invalid("interp_bspline_backward: d_C must not overlap an input");
-    if (need_u && (overlaps(d_u, ubytes, go, gbytes) || overlaps(d_u, ubytes, u, ubytes) || overlaps(d_u, ubytes, C, cbytes)))
-        return fail_invalid("interp_bspline_backward: d_u must not overlap an input");
-    if (need_C && need_u && overlaps(d_C, cbytes, d_u, ubytes))
-        return fail_invalid("interp_bspline_backward: d_C and d_u must not overlap each other");
-    if (need_C) LAGO_HIP_TRY(hipMemsetAsync(d_C, 0, cbytes, s));   // the scatter target
+    const GatherBytes b(sizeof(R), sizeof(R), dim, nn, nc, v.nvox, v.nvox, bc);
+    const int rc = check_gather_backward("interp_bspline_backward", d_C, d_u, go, C, u, b, need_C != 0, need_u != 0, empty, s);
+    if (rc != kLaunchNow) return rc;
     hipError_t e = hipSuccess;
     with_dim(dim, [&](auto DIM) {
         with_flags([&](auto BC, auto NEED_C, auto NEED_U) {
-            if constexpr (NEED_C() || NEED_U())   // (neither: returned above)
+            if constexpr (NEED_C() || NEED_U())   // (neither: the call was done above)
                 e = launch(interp_bspline_bwd_kernel<R, DIM(), BC(), NEED_C(), NEED_U()>, dim3(g.nblocks), dim3(kBlock), 0, s, d_C,
                            d_u, go, C, u, dt, (int)nc, g);
         }, bc != 0, need_C != 0, need_u != 0);
     });
-    if (e != hipSuccess) return fail_hip(e, "interp_bspline_backward");
-    return finish_launch(s, "interp_bspline_backward");
+    return launched(e, s, "interp_bspline_backward");
 }
 
 }  // namespace lago

@@ -20,6 +20,7 @@
 #include <stdio.h>
 
 #include "../../include/lagomorph_hip.h"
+#include "args.hpp"     // Volume / check_volume, Span / any_overlap, the gather argument checks (host only)
 
 namespace lago {
 
@@ -112,38 +113,30 @@ struct Geom {
 // order, so the block order of such a launch shows in the last bits of its result: it is then always ascending and the
 // call leaves the alternation counter alone -- the bits of a scatter-add never depend on which calls (of any kind, valid
 // or rejected) this process has made before (tests/test_gpu_dispatch.py: test_scatter_direction_is_history_free).
-inline bool make_geom(Geom &g, int dim, int64_t nn, int64_t nx, int64_t ny, int64_t nz, int vox_per_block = kBlock,
-                      bool scatter = false) {
-    // one channel of one batch item is addressed with 32-bit byte offsets: nvox * 8 < 2^32
-    if (dim == 2) {
-        nz = ny;
-        ny = nx;
-        nx = 1;
-    }
-    if (nn < 0 || nx < 1 || ny < 1 || nz < 1) return false;
-    int64_t nv = nx * ny * nz;
-    if (nv >= (1ll << 29)) return false;
-    g.nx = (int)nx;
-    g.ny = (int)ny;
-    g.nz = (int)nz;
-    g.nvox = (uint32_t)nv;
-    g.nbx = (uint32_t)((nv + vox_per_block - 1) / vox_per_block);
+inline bool make_geom(Geom &g, const Volume &v, int64_t nn, int vox_per_block = kBlock, bool scatter = false) {
+    // one channel of one batch item is addressed with 32-bit byte offsets: nvox * 8 < 2^32 (args.hpp: kPlane29)
+    if (nn < 0 || v.nvox < 1 || v.nvox > kPlane29.max_nvox) return false;
+    g.nx = (int)v.nx;
+    g.ny = (int)v.ny;
+    g.nz = (int)v.nz;
+    g.nvox = (uint32_t)v.nvox;
+    g.nbx = (uint32_t)((v.nvox + vox_per_block - 1) / vox_per_block);
     int64_t nb = (int64_t)g.nbx * nn;
     if (nb >= (1ll << 31)) return false;
     g.nblocks = (uint32_t)nb;
     g.rev = scatter ? 0 : next_direction();
-    g.dyz = FastDiv((uint32_t)(ny * nz));
-    g.dz = FastDiv((uint32_t)nz);
+    g.dyz = FastDiv((uint32_t)(v.ny * v.nz));
+    g.dz = FastDiv((uint32_t)v.nz);
     g.dnbx = FastDiv(g.nbx);
     return true;
 }
-
-// argument checks that several entry points share
-inline bool overlaps(const void *a, size_t na, const void *b, size_t nb) {  // [a, a + na) and [b, b + nb) bytes
-    const uintptr_t p = (uintptr_t)a, q = (uintptr_t)b;
-    return p < q + nb && q < p + na;
+// ... from raw extents (dim == 2: (nx, ny) = (H, W), nz ignored), for the entry points that report one "bad extent"
+inline bool make_geom(Geom &g, int dim, int64_t nn, int64_t nx, int64_t ny, int64_t nz, int vox_per_block = kBlock,
+                      bool scatter = false) {
+    Volume v;
+    return geom_volume(v, dim, nn, nx, ny, nz) && make_geom(g, v, nn, vox_per_block, scatter);
 }
-inline bool overlaps(const void *a, const void *b, size_t bytes) { return overlaps(a, bytes, b, bytes); }
+
 inline bool thin(int dim, int64_t nx, int64_t ny, int64_t nz) {  // an extent the central differences cannot take
     return nx <= 1 || ny <= 1 || (dim == 3 && nz <= 1);
 }

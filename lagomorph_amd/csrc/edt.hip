@@ -121,22 +121,19 @@ static hipError_t edt_pass_launch(float *io, const int32_t *L, const EdtArgs &p,
 
 static int distance_transform_impl(float *out, const int32_t *L, int where, int32_t label, const double *spacing, int squared,
                                    int dim, int64_t nn, int64_t nx, int64_t ny, int64_t nz, void *stream) {
-    if (dim != 2 && dim != 3) return fail_invalid("distance_transform: Only two- and three-dimensional label maps are supported (dim %d)", dim);
+    if (const int rc = check_dim("distance_transform", dim)) return rc;
     if (where != LAGO_EDT_NONZERO && where != LAGO_EDT_EQUAL && where != LAGO_EDT_NOT_EQUAL && where != LAGO_EDT_SURFACE)
         return fail_invalid("distance_transform: where must be one of LAGO_EDT_*, got %d", where);
     if (!spacing) return fail_invalid("distance_transform: null pointer");
     for (int a = 0; a < dim; ++a)
         if (!(spacing[a] > 0.0) || !((float)spacing[a] > 0.0f) || !((float)spacing[a] < __builtin_inff()))
             return fail_invalid("distance_transform: spacing must be positive and finite in float32 (axis %d: %g)", a, spacing[a]);
-    if (dim == 2) {   // (H, W) as (1, H, W): the same flattened layout
-        nz = ny;
-        ny = nx;
-        nx = 1;
-    }
-    if (nn < 0 || nx < 0 || ny < 0 || nz < 0) return fail_invalid("distance_transform: bad extent");
+    Volume v;   // (the extents are bounded just below)
+    if (const int rc = check_volume(v, "distance_transform", dim, nx, ny, nz, kPlaneAny, {nn})) return rc;
+    as_volume(dim, nx, ny, nz);
     if (nx > EDT_MAX_EXTENT || ny > EDT_MAX_EXTENT || nz > EDT_MAX_EXTENT)
         return fail_invalid("distance_transform: an extent above %d (%lld, %lld, %lld)", EDT_MAX_EXTENT, (long long)nx, (long long)ny, (long long)nz);
-    if (nn == 0 || nx == 0 || ny == 0 || nz == 0) return LAGO_OK;   // nothing to write
+    if (nn == 0 || v.nvox == 0) return LAGO_OK;   // nothing to write
     if (!out || !L) return fail_invalid("distance_transform: null pointer");
     const int64_t rows = nn * nx * ny;
     // no pass has more workgroups than there are voxels
@@ -169,9 +166,8 @@ static int distance_transform_impl(float *out, const int32_t *L, int where, int3
         p.s = sx;
         p.inner = (uint32_t)(ny * nz);
         e = edt_pass_launch<false>(out, L, p, !squared, (uint32_t)nn, s);
-        if (e != hipSuccess) return fail_hip(e, "distance_transform");
     }
-    return finish_launch(s, "distance_transform");
+    return launched(e, s, "distance_transform");
 }
 
 }  // namespace lago

@@ -38,8 +38,6 @@
 // Every LDS index stays inside the launch's allocation for any spacing in 1..32 and any extent, partial tiles included:
 // a coordinate l of a tile has the offset (g0 + l) / s - g0 / s <= (T - 1 + s - 1) / s = C - 4, whether or not the
 // voxel exists, and control points beyond the lattice are staged as 0 and never loaded.
-#include <limits.h>
-
 #include "common.hpp"
 #include "ffd_weights.hpp"
 
@@ -279,25 +277,15 @@ __global__ __launch_bounds__(256) void ffd_restrict_sum_kernel(R *__restrict__ d
 // The checks every entry point shares, before any device call.  LAGO_OK with `empty` set: nothing to do.
 static int ffd_geom(const char *what, FfdGeom &g, bool &empty, int dim, int64_t rows, int64_t nx, int64_t ny, int64_t nz,
                     int sx, int sy, int sz) {
-    if (dim != 2 && dim != 3) return fail_invalid("%s: Only two- and three-dimensional fields are supported (dim %d)", what, dim);
-    if (dim == 2) {   // (ny, nz) = (H, W), as Geom
-        nz = ny;
-        ny = nx;
-        nx = 1;
-        sz = sy;
-        sy = sx;
-        sx = 1;
-    }
-    if (rows < 0 || nx < 0 || ny < 0 || nz < 0) return fail_invalid("%s: negative extent", what);
+    Volume v;
+    if (const int rc = check_volume(v, what, dim, nx, ny, nz, kPlane29, {rows})) return rc;
+    if (dim == 2) sz = sy, sy = sx, sx = 1;   // the spacings follow the extents to (1, H, W)
     if (sx < 1 || sx > kFfdMaxSpacing || sy < 1 || sy > kFfdMaxSpacing || sz < 1 || sz > kFfdMaxSpacing)
         return fail_invalid("%s: a spacing outside 1..%d", what, kFfdMaxSpacing);
-    if (nx > INT_MAX || ny > INT_MAX || nz > INT_MAX) return fail_invalid("%s: an extent of 2^31 or more", what);
-    const int64_t nxy = nx * ny;
-    if (nxy >= (1ll << 29) || nxy * nz >= (1ll << 29)) return fail_invalid("%s: a plane of 2^29 elements or more", what);
-    empty = rows == 0 || nxy * nz == 0;
+    empty = rows == 0 || v.nvox == 0;
     if (empty) return LAGO_OK;
     if (rows >= (1ll << 31)) return fail_invalid("%s: 2^31 rows or more", what);
-    const int64_t n[3] = {nx, ny, nz};
+    const int64_t n[3] = {v.nx, v.ny, v.nz};
     const int s[3] = {sx, sy, sz};
     const int tile[3] = {dim == 3 ? FfdTile<3>::TX : FfdTile<2>::TX, dim == 3 ? FfdTile<3>::TY : FfdTile<2>::TY, kFfdTZ};
     int64_t mvox = 1, ntiles = 1;
@@ -315,7 +303,7 @@ static int ffd_geom(const char *what, FfdGeom &g, bool &empty, int dim, int64_t 
     const int64_t bpr = (mvox + 255) / 256;
     if (ntiles * rows >= (1ll << 31) || bpr * rows >= (1ll << 31)) return fail_invalid("%s: too many tiles for one launch", what);
     g.ntiles = (uint32_t)ntiles;
-    g.nvox = (uint32_t)(nxy * nz);
+    g.nvox = (uint32_t)v.nvox;
     g.mvox = (uint32_t)mvox;
     g.bpr = (uint32_t)bpr;
     g.dtiles = FastDiv(g.ntiles);
@@ -350,8 +338,7 @@ static int ffd_expand_impl(R *out, const R *ctrl, int dim, int64_t rows, int64_t
         const size_t smem = (4 * T::COORDS + asz + (size_t)T::TX * g.c[1] * g.c[2]) * sizeof(R) + T::COORDS * sizeof(int);
         e = launch(ffd_expand_kernel<R, DIM()>, dim3(g.ntiles * (uint32_t)rows), dim3(256), smem, s, out, ctrl, g);
     });
-    if (e != hipSuccess) return fail_hip(e, "ffd_expand");
-    return finish_launch(s, "ffd_expand");
+    return launched(e, s, "ffd_expand");
 }
 
 template <typename R>
@@ -367,7 +354,7 @@ static int ffd_expand_adjoint_impl(R *d_ctrl, const R *go, R *scratch, int64_t s
         return fail_invalid("ffd_expand_adjoint: scratch of %lld elements, %lld needed (lago_ffd_scratch_elems)", (long long)scratch_elems,
                             (long long)need);
     const size_t cb = (size_t)rows * g.mvox * sizeof(R), gb = (size_t)rows * g.nvox * sizeof(R), sb = (size_t)need * sizeof(R);
-    if (overlaps(d_ctrl, cb, go, gb) || overlaps(d_ctrl, cb, scratch, sb) || overlaps(scratch, sb, go, gb))
+    if (any_overlap({{d_ctrl, cb}, {scratch, sb}}, {{go, gb}}))
         return fail_invalid("ffd_expand_adjoint: d_ctrl, grad_out and scratch must not overlap");
     hipStream_t s = (hipStream_t)stream;
     hipError_t e = hipSuccess;
@@ -379,8 +366,7 @@ static int ffd_expand_adjoint_impl(R *d_ctrl, const R *go, R *scratch, int64_t s
         if (e == hipSuccess)
             e = launch(ffd_restrict_sum_kernel<R, DIM()>, dim3(g.bpr * (uint32_t)rows), dim3(256), 0, s, d_ctrl, (const R *)scratch, g);
     });
-    if (e != hipSuccess) return fail_hip(e, "ffd_expand_adjoint");
-    return finish_launch(s, "ffd_expand_adjoint");
+    return launched(e, s, "ffd_expand_adjoint");
 }
 
 }  // namespace lago

@@ -277,8 +277,7 @@ int fluid_xpass_launch(float *F, const float *tab, int inverse, int64_t nn, int6
     else if (nx == 128) e = xpass_launch<7>(Fc, tab, inverse, nn, ny, nzc, (float)scale, s);
     else if (nx == 256) e = xpass_launch<8>(Fc, tab, inverse, nn, ny, nzc, (float)scale, s);
     else return fail_invalid("fluid_xpass: unsupported nx");
-    if (e != hipSuccess) return fail_hip(e, "fluid_xpass");
-    return finish_launch(s, "fluid_xpass");
+    return launched(e, s, "fluid_xpass");
 }
 
 }  // namespace lago

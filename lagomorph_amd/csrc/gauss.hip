@@ -182,7 +182,7 @@ static int gauss_impl(R *out, const R *in, R *scratch, const int *radii, const d
     }
     if (m >= 2) {
         if (!scratch) return fail_invalid("gaussian_smooth: two or more passes need the scratch tensor");
-        if (overlaps(scratch, in, bytes) || overlaps(scratch, out, bytes))
+        if (any_overlap({{scratch, bytes}}, {{in, bytes}, {out, bytes}}))
             return fail_invalid("gaussian_smooth: scratch must not alias in or out");
     }
     // pass.vec was planned against `out`; the scratch tensor must allow the same stores

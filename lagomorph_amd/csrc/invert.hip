@@ -157,7 +157,7 @@ static int invert_adjoint_impl(R *lam, const R *go, const R *u, const R *v, int 
     if (g.nblocks == 0) return LAGO_OK;
     if (!lam || !go || !u || !v) return fail_invalid("invert_displacement_adjoint: null pointer");
     const size_t bytes = (size_t)nn * dim * g.nvox * sizeof(R);
-    if (overlaps(lam, u, bytes) || overlaps(lam, v, bytes) || overlaps(lam, go, bytes))
+    if (any_overlap({{lam, bytes}}, {{u, bytes}, {v, bytes}, {go, bytes}}))
         return fail_invalid("invert_displacement_adjoint: lam must not alias an input");
     hipStream_t s = (hipStream_t)stream;
     with_dim(dim, [&](auto DIM) {

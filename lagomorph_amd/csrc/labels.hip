@@ -165,19 +165,17 @@ __global__ __launch_bounds__(kBlock) void warp_labels3_unroll_kernel(int32_t *__
 template <typename R>
 static int warp_labels_impl(int32_t *out, const int32_t *L, const R *u, double dt, int mode, int bc, int dim, int64_t nn,
                             int64_t nx, int64_t ny, int64_t nz, void *stream) {
-    if (dim != 2 && dim != 3) return fail_invalid("warp_labels: Only two- and three-dimensional label maps are supported (dim %d)", dim);
+    if (const int rc = check_dim("warp_labels", dim)) return rc;
     if (mode != LAGO_LABELS_NEAREST && mode != LAGO_LABELS_VOTE)
         return fail_invalid("warp_labels: mode must be LAGO_LABELS_NEAREST or LAGO_LABELS_VOTE, got %d", mode);
-    if (dim == 2) nz = 1;
-    if (nn < 0 || nx < 0 || ny < 0 || nz < 0) return fail_invalid("warp_labels: bad extent");
-    if (nn == 0 || nx == 0 || ny == 0 || nz == 0) return LAGO_OK;   // nothing to write
+    Volume v;
+    if (const int rc = check_volume(v, "warp_labels", dim, nx, ny, nz, kPlane29, {nn})) return rc;
+    if (nn == 0 || v.nvox == 0) return LAGO_OK;   // nothing to write
     Geom g;
-    if (!make_geom(g, dim, nn, nx, ny, nz)) return fail_invalid("warp_labels: bad extent");
-    if (!out || !L || !u) return fail_invalid("warp_labels: null pointer");
-    const size_t obytes = (size_t)nn * g.nvox * 4, lbytes = (size_t)(bc ? 1 : nn) * g.nvox * 4,
-                 ubytes = (size_t)nn * dim * g.nvox * sizeof(R);
-    if (overlaps(out, obytes, L, lbytes) || overlaps(out, obytes, u, ubytes))
-        return fail_invalid("warp_labels: out must not overlap an input");
+    if (!make_geom(g, v, nn)) return fail_invalid("warp_labels: bad extent");
+    // one 4-byte label a voxel, gathered at the voxels' own positions
+    if (const int rc = check_gather("warp_labels", out, L, u, GatherBytes(4, sizeof(R), dim, nn, 1, v.nvox, v.nvox, bc)); rc != kLaunchNow)
+        return rc;
     hipStream_t s = (hipStream_t)stream;
     constexpr int U = 2;
     hipError_t e = hipSuccess;
@@ -194,8 +192,7 @@ static int warp_labels_impl(int32_t *out, const int32_t *L, const R *u, double d
             }, bc != 0, mode == LAGO_LABELS_VOTE);
         });
     }
-    if (e != hipSuccess) return fail_hip(e, "warp_labels");
-    return finish_launch(s, "warp_labels");
+    return launched(e, s, "warp_labels");
 }
 
 // ------------------------------------------------------------------ label_overlap
@@ -338,16 +335,14 @@ static int label_overlap_impl(long long *counts, const int32_t *A, const int32_t
     const uint32_t groups = (K3 + 63) / 64;   // of the reducer
     if (nb >= (1ull << 31) || (uint64_t)rows * groups >= (1ull << 31)) return fail_invalid("label_overlap: bad extent");
     const size_t ibytes = (size_t)rows * p.nvox * 4, sbytes = (size_t)nb * K3 * 4, cbytes = (size_t)rows * K3 * 8;
-    if (overlaps(scratch, sbytes, A, ibytes) || overlaps(scratch, sbytes, B, ibytes) || overlaps(counts, cbytes, A, ibytes) ||
-        overlaps(counts, cbytes, B, ibytes) || overlaps(counts, cbytes, scratch, sbytes))
+    if (any_overlap({{counts, cbytes}, {scratch, sbytes}}, {{A, ibytes}, {B, ibytes}}))
         return fail_invalid("label_overlap: counts and scratch must not overlap an input or each other");
     hipStream_t s = (hipStream_t)stream;
     hipError_t e = launch(label_overlap_kernel, dim3((uint32_t)nb), dim3(kBlock), (size_t)p.rep * K3 * 4, s, scratch, A, B, p);
     if (e != hipSuccess) return fail_hip(e, "label_overlap");
     e = launch(label_overlap_reduce_kernel, dim3((uint32_t)rows * groups), dim3(kBlock), 0, s, counts, (const uint32_t *)scratch,
                p.chunks, K3, groups);
-    if (e != hipSuccess) return fail_hip(e, "label_overlap");
-    return finish_launch(s, "label_overlap");
+    return launched(e, s, "label_overlap");
 }
 
 }  // namespace lago

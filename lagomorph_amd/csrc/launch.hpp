@@ -61,6 +61,9 @@ inline hipError_t launch(void (*kernel)(P...), dim3 grid, dim3 block, size_t sme
     return hipSuccess;
 }
 
+// How an entry point ends after its last launch(): the failure launch() returned, else what finish_launch finds.
+inline int launched(hipError_t e, hipStream_t s, const char *what) { return e != hipSuccess ? fail_hip(e, what) : finish_launch(s, what); }
+
 // Grid of the slab-unrolled 3D gather kernels (U voxels per lane, kBlock lanes): false when the volume is too flat or
 // too small for them, or the grid too large; otherwise nbx_u blocks per batch item, nb in all.
 inline bool slab_grid(const Geom &g, int64_t nn, int U, uint32_t &nbx_u, uint32_t &nb) {

@@ -192,13 +192,12 @@ static int lncc_moments_impl(R *out, const R *I, const R *J, R *scratch, const i
     if (g.nblocks == 0) return LAGO_OK;
     if (!out || !I || !J) return fail_invalid("lncc_moments: null pointer");
     const size_t bytes = (size_t)rows * g.nvox * sizeof(R);
-    if (overlaps(out, 5 * bytes, I, bytes) || overlaps(out, 5 * bytes, J, bytes))
+    if (any_overlap({{out, 5 * bytes}}, {{I, bytes}, {J, bytes}}))
         return fail_invalid("lncc_moments: out must not alias an input");
     const int later = (rad[0] > 0) + (rad[1] > 0);   // passes after the moments pass, x before y
     if (later) {
         if (!scratch) return fail_invalid("lncc_moments: a filtered axis besides the last needs the scratch tensor");
-        if (overlaps(scratch, 5 * bytes, I, bytes) || overlaps(scratch, 5 * bytes, J, bytes) ||
-            overlaps(scratch, out, 5 * bytes))
+        if (any_overlap({{scratch, 5 * bytes}}, {{I, bytes}, {J, bytes}, {out, 5 * bytes}}))
             return fail_invalid("lncc_moments: scratch must not alias an input or out");
     }
     hipStream_t s = (hipStream_t)stream;
@@ -235,8 +234,7 @@ static int lncc_pointwise(const char *name, int64_t n, std::initializer_list<con
     hipStream_t s = (hipStream_t)stream;
     hipError_t e = hipSuccess;
     with_flags([&](auto VEC) { e = f(VEC, grid, s); }, vec);
-    if (e != hipSuccess) return fail_hip(e, name);
-    return finish_launch(s, name);
+    return launched(e, s, name);
 }
 
 template <typename R>
@@ -261,7 +259,7 @@ static int lncc_coeffs_impl(R *coef, const R *mom, const R *g, double eps, int w
     if (!coef || !mom || !g) return fail_invalid("lncc_coeffs: null pointer");
     const size_t bytes = (size_t)n * sizeof(R);
     const size_t cbytes = (which == 3 ? 5 : 3) * bytes;
-    if (overlaps(coef, cbytes, mom, 5 * bytes) || overlaps(coef, cbytes, g, bytes))
+    if (any_overlap({{coef, cbytes}}, {{mom, 5 * bytes}, {g, bytes}}))
         return fail_invalid("lncc_coeffs: coef must not alias an input");
     return lncc_pointwise<R>("lncc_coeffs", n, {coef, mom, g}, stream, [&](auto VEC, dim3 grid, hipStream_t s) {
         hipError_t e = hipSuccess;
@@ -280,12 +278,8 @@ static int lncc_combine_impl(R *dI, R *dJ, const R *sm, const R *I, const R *J, 
     if (!sm || !I || !J || ((which & 1) && !dI) || ((which & 2) && !dJ)) return fail_invalid("lncc_combine: null pointer");
     const size_t bytes = (size_t)n * sizeof(R);
     R *const outs[2] = {(which & 1) ? dI : nullptr, (which & 2) ? dJ : nullptr};   // (an output not asked for is ignored)
-    for (R *d : outs) {
-        if (!d) continue;
-        if (overlaps(d, bytes, sm, (which == 3 ? 5 : 3) * bytes) || overlaps(d, I, bytes) || overlaps(d, J, bytes))
-            return fail_invalid("lncc_combine: an output must not alias an input");
-    }
-    if (which == 3 && overlaps(dI, dJ, bytes)) return fail_invalid("lncc_combine: dI must not alias dJ");
+    if (any_overlap({{outs[0], bytes}, {outs[1], bytes}}, {{sm, (which == 3 ? 5 : 3) * bytes}, {I, bytes}, {J, bytes}}))
+        return fail_invalid("lncc_combine: an output must not alias an input or the other output");
     return lncc_pointwise<R>("lncc_combine", n, {sm, I, J, outs[0], outs[1]}, stream,
                              [&](auto VEC, dim3 grid, hipStream_t s) {
         hipError_t e = hipSuccess;

@@ -186,7 +186,7 @@ __global__ __launch_bounds__(kBlock) void mi_bwd_kernel(R *dI, R *dJ, const doub
 // what the two entry points check alike; nvox = 0: nothing to do (with LAGO_OK)
 static int mi_check(const char *name, int bins, double loI, double hiI, double loJ, double hiJ, int dim, int64_t rows,
                     int64_t nx, int64_t ny, int64_t nz, MiArgs &p) {
-    if (dim != 2 && dim != 3) return fail_invalid("%s: Only two- and three-dimensional fields are supported (dim %d)", name, dim);
+    if (const int rc = check_dim(name, dim)) return rc;
     if (bins < LAGO_MI_MIN_BINS || bins > LAGO_MI_MAX_BINS)
         return fail_invalid("%s: bins must be in %d..%d, got %d", name, LAGO_MI_MIN_BINS, LAGO_MI_MAX_BINS, bins);
     p.B = bins;
@@ -198,11 +198,10 @@ static int mi_check(const char *name, int bins, double loI, double hiI, double l
             !(ax->s > 0.0 && ax->s <= 1.7976931348623157e308))
             return fail_invalid("%s: a range needs finite bounds lo < hi with a finite bin scale, got (%g, %g)", name, ax->lo, ax->hi);
     }
-    if (dim == 2) nz = 1;
-    if (rows < 0 || nx < 0 || ny < 0 || nz < 0 || rows >= (1ll << 31)) return fail_invalid("%s: bad extent", name);
-    if (nx > (1ll << 30) || ny > (1ll << 30) || nz > (1ll << 30) || nx * ny > (1ll << 30) || nx * ny * nz > (1ll << 30))
-        return fail_invalid("%s: more than 2^30 voxels in a row", name);
-    p.nvox = (uint32_t)(nx * ny * nz);
+    Volume v;
+    if (const int rc = check_volume(v, name, dim, nx, ny, nz, kPlane30, {rows})) return rc;
+    if (rows >= (1ll << 31)) return fail_invalid("%s: 2^31 rows or more", name);
+    p.nvox = (uint32_t)v.nvox;
     return LAGO_OK;
 }
 
@@ -241,8 +240,7 @@ static int mi_histogram_impl(double *P, const R *I, const R *J, long long *scrat
     const uint32_t groups = (uint32_t)((BB + 63) / 64);   // of the reducer
     if (nb >= (1ull << 31) || (uint64_t)rows * groups >= (1ull << 31)) return fail_invalid("mi_histogram: bad extent");
     const size_t ibytes = (size_t)rows * p.nvox * sizeof(R), sbytes = (size_t)nb * BB * 8, pbytes = (size_t)rows * BB * 8;
-    if (overlaps(scratch, sbytes, I, ibytes) || overlaps(scratch, sbytes, J, ibytes) || overlaps(P, pbytes, I, ibytes) ||
-        overlaps(P, pbytes, J, ibytes) || overlaps(P, pbytes, scratch, sbytes))
+    if (any_overlap({{P, pbytes}, {scratch, sbytes}}, {{I, ibytes}, {J, ibytes}}))
         return fail_invalid("mi_histogram: P and scratch must not alias an input or each other");
     hipStream_t s = (hipStream_t)stream;
     // as many replicas of the table as 64 KB hold, eight at most: B <= 32 eight, B <= 45 four, else two
@@ -255,8 +253,7 @@ static int mi_histogram_impl(double *P, const R *I, const R *J, long long *scrat
     if (e != hipSuccess) return fail_hip(e, "mi_histogram");
     e = launch(mi_reduce_kernel, dim3((uint32_t)rows * groups), dim3(kBlock), 0, s, P, (const long long *)scratch, p.chunks,
                (uint32_t)BB, groups, (double)p.nvox * kMiOne);
-    if (e != hipSuccess) return fail_hip(e, "mi_histogram");
-    return finish_launch(s, "mi_histogram");
+    return launched(e, s, "mi_histogram");
 }
 
 template <typename R>
@@ -273,11 +270,8 @@ static int mi_backward_impl(R *dI, R *dJ, const double *G, const R *I, const R *
     const uint64_t nb = (uint64_t)rows * p.chunks;
     if (nb >= (1ull << 31)) return fail_invalid("mi_backward: bad extent");
     const size_t ibytes = (size_t)rows * p.nvox * sizeof(R), gbytes = (size_t)rows * BB * 8;
-    for (R *d : {dI, dJ}) {
-        if (d && (overlaps(d, I, ibytes) || overlaps(d, J, ibytes) || overlaps(d, ibytes, G, gbytes)))
-            return fail_invalid("mi_backward: an output must not alias an input");
-    }
-    if (dI && dJ && overlaps(dI, dJ, ibytes)) return fail_invalid("mi_backward: dI must not alias dJ");
+    if (any_overlap({{dI, ibytes}, {dJ, ibytes}}, {{I, ibytes}, {J, ibytes}, {G, gbytes}}))
+        return fail_invalid("mi_backward: an output must not alias an input or the other output");
     hipStream_t s = (hipStream_t)stream;
     hipError_t e = hipSuccess;
     with_flags([&](auto NEED_I, auto NEED_J) {
@@ -285,8 +279,7 @@ static int mi_backward_impl(R *dI, R *dJ, const double *G, const R *I, const R *
             e = launch(mi_bwd_kernel<R, NEED_I(), NEED_J()>, dim3((uint32_t)nb), dim3(kBlock), (size_t)BB * 8, s, dI, dJ, G,
                        I, J, p);
     }, dI != nullptr, dJ != nullptr);
-    if (e != hipSuccess) return fail_hip(e, "mi_backward");
-    return finish_launch(s, "mi_backward");
+    return launched(e, s, "mi_backward");
 }
 
 }  // namespace lago

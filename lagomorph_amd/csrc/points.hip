@@ -21,8 +21,6 @@
 // Every corner index is clamped before it is used (clamp1 is one v_med3_i32 on whatever integer the conversion gave),
 // so no position, finite or not, addresses outside F or d_F.  Bytes per point and the resource usage of both kernels
 // are in DESIGN.md; no LDS, no scratch.
-#include <limits.h>
-
 #include "common.hpp"
 
 #ifndef LAGO_NT_POINTS_ST
@@ -131,28 +129,13 @@ __global__ __launch_bounds__(kBlock) void interp_points_bwd_kernel(R *__restrict
 // The checks both entry points share, before any device call.  LAGO_OK with `empty` set: nothing to do.
 static int points_geom(const char *what, PtGeom &g, bool &empty, int dim, int64_t nn, int64_t nc, int64_t np, int64_t nx,
                        int64_t ny, int64_t nz, size_t elem) {
-    if (dim != 2 && dim != 3) return fail_invalid("%s: Only two- and three-dimensional fields are supported (dim %d)", what, dim);
-    if (dim == 2) {   // (ny, nz) = (H, W), as Geom
-        nz = ny;
-        ny = nx;
-        nx = 1;
-    }
-    if (nn < 0 || nc < 0 || np < 0 || nx < 0 || ny < 0 || nz < 0) return fail_invalid("%s: negative extent", what);
-    if (nx > INT_MAX || ny > INT_MAX || nz > INT_MAX) return fail_invalid("%s: an extent of 2^31 or more", what);
-    // one channel plane is addressed with 32-bit byte offsets (nx ny < 2^62 and, once that is below 2^32, nx ny nz
-    // < 2^63: the products cannot wrap)
-    const int64_t nxy = nx * ny;
-    if (nxy >= (1ll << 32) || nxy * nz >= (1ll << 32) / (int64_t)elem)
-        return fail_invalid("%s: a channel plane of 2^32 bytes or more", what);
+    Volume v;   // one channel plane is addressed with 32-bit byte offsets
+    if (const int rc = check_volume(v, what, dim, nx, ny, nz, plane_bytes32(elem), {nn, nc, np})) return rc;
     if (np >= (1ll << 31)) return fail_invalid("%s: 2^31 points or more per item", what);
     if (nc > INT_MAX) return fail_invalid("%s: 2^31 channels or more", what);
-    empty = nn == 0 || nc == 0 || np == 0 || nxy * nz == 0;
+    empty = nn == 0 || nc == 0 || np == 0 || v.nvox == 0;
     if (!empty && nn > 65535) return fail_invalid("%s: more than 65535 batch items", what);   // the grid's second axis
-    g.nx = (int)nx;
-    g.ny = (int)ny;
-    g.nz = (int)nz;
-    g.nvox = (uint32_t)(nxy * nz);
-    g.np = (uint32_t)np;
+    g = {(int)v.nx, (int)v.ny, (int)v.nz, (uint32_t)v.nvox, (uint32_t)np};
     return LAGO_OK;
 }
 
@@ -163,11 +146,8 @@ static int interp_points_impl(R *out, const R *F, const R *x, int dim, int64_t n
     bool empty;
     if (const int rc = points_geom("interp_points", g, empty, dim, nn, nc, np, nx, ny, nz, sizeof(R))) return rc;
     if (empty) return LAGO_OK;   // nothing to write
-    if (!out || !F || !x) return fail_invalid("interp_points: null pointer");
-    const size_t obytes = (size_t)nn * nc * g.np * sizeof(R), fbytes = (size_t)(bc ? 1 : nn) * nc * g.nvox * sizeof(R),
-                 xbytes = (size_t)nn * dim * g.np * sizeof(R);
-    if (overlaps(out, obytes, F, fbytes) || overlaps(out, obytes, x, xbytes))
-        return fail_invalid("interp_points: out must not overlap an input");
+    const GatherBytes b(sizeof(R), sizeof(R), dim, nn, nc, g.np, g.nvox, bc);
+    if (const int rc = check_gather("interp_points", out, F, x, b); rc != kLaunchNow) return rc;
     hipStream_t s = (hipStream_t)stream;
     const dim3 grid((g.np + kBlock - 1) / kBlock, (uint32_t)nn);
     hipError_t e = hipSuccess;
@@ -176,8 +156,7 @@ static int interp_points_impl(R *out, const R *F, const R *x, int dim, int64_t n
             e = launch(interp_points_fwd_kernel<R, DIM(), BC()>, grid, dim3(kBlock), 0, s, out, F, x, (int)nc, g);
         }, bc != 0);
     });
-    if (e != hipSuccess) return fail_hip(e, "interp_points");
-    return finish_launch(s, "interp_points");
+    return launched(e, s, "interp_points");
 }
 
 template <typename R>
@@ -188,34 +167,19 @@ static int interp_points_backward_impl(R *d_F, R *d_x, const R *go, const R *F, 
     bool empty;
     if (const int rc = points_geom("interp_points_backward", g, empty, dim, nn, nc, np, nx, ny, nz, sizeof(R))) return rc;
     hipStream_t s = (hipStream_t)stream;
-    const size_t fbytes = (size_t)(bc ? 1 : nn) * nc * g.nvox * sizeof(R);
-    if (empty) {   // no point adds anything: a d_F that has cells is all zeros, a d_x has no element or only empty sums
-        if (need_F && d_F && fbytes) LAGO_HIP_TRY(hipMemsetAsync(d_F, 0, fbytes, s));
-        const size_t xb = (size_t)nn * dim * g.np * sizeof(R);
-        if (need_x && d_x && xb) LAGO_HIP_TRY(hipMemsetAsync(d_x, 0, xb, s));
-        return LAGO_OK;
-    }
-    if (!need_F && !need_x) return LAGO_OK;
-    if ((need_F && !d_F) || (need_x && (!d_x || !F)) || !go || !x) return fail_invalid("interp_points_backward: null pointer");
-    const size_t gbytes = (size_t)nn * nc * g.np * sizeof(R), xbytes = (size_t)nn * dim * g.np * sizeof(R);
-    if (need_F && (overlaps(d_F, fbytes, go, gbytes) || overlaps(d_F, fbytes, x, xbytes) || (F && overlaps(d_F, fbytes, F, fbytes))))
-        return fail_invalid("interp_points_backward: d_F must not overlap an input");
-    if (need_x && (overlaps(d_x, xbytes, go, gbytes) || overlaps(d_x, xbytes, x, xbytes) || overlaps(d_x, xbytes, F, fbytes)))
-        return fail_invalid("interp_points_backward: d_x must not overlap an input");
-    if (need_F && need_x && overlaps(d_F, fbytes, d_x, xbytes))
-        return fail_invalid("interp_points_backward: d_F and d_x must not overlap each other");
-    if (need_F) LAGO_HIP_TRY(hipMemsetAsync(d_F, 0, fbytes, s));   // the scatter target
+    const GatherBytes b(sizeof(R), sizeof(R), dim, nn, nc, g.np, g.nvox, bc);
+    const int rc = check_gather_backward("interp_points_backward", d_F, d_x, go, F, x, b, need_F != 0, need_x != 0, empty, s);
+    if (rc != kLaunchNow) return rc;
     const dim3 grid((g.np + kBlock - 1) / kBlock, (uint32_t)nn);
     hipError_t e = hipSuccess;
     with_dim(dim, [&](auto DIM) {
         with_flags([&](auto BC, auto NEED_F, auto NEED_X) {
-            if constexpr (NEED_F() || NEED_X())   // (neither: returned above)
+            if constexpr (NEED_F() || NEED_X())   // (neither: the call was done above)
                 e = launch(interp_points_bwd_kernel<R, DIM(), BC(), NEED_F(), NEED_X()>, grid, dim3(kBlock), 0, s, d_F, d_x,
                            go, F, x, (int)nc, g);
         }, bc != 0, need_F != 0, need_x != 0);
     });
-    if (e != hipSuccess) return fail_hip(e, "interp_points_backward");
-    return finish_launch(s, "interp_points_backward");
+    return launched(e, s, "interp_points_backward");
 }
 
 }  // namespace lago

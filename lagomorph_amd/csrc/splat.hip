@@ -804,9 +804,8 @@ static bool make_shear(ShearGeom &sg, const Geom &g, int64_t nn, size_t &smem, i
 
 // What follows the launch of an interp_backward splat: its error, or the path counter and the launch check.
 static int splat_launched(hipError_t e, hipStream_t s, int path, const char *what) {
-    if (e != hipSuccess) return fail_hip(e, what);
-    note_path(path);
-    return finish_launch(s, what);
+    if (e == hipSuccess) note_path(path);
+    return launched(e, s, what);
 }
 
 // float32 displacement splat through the sheared-window kernel; returns 1 when the shape is left to the
@@ -998,8 +997,7 @@ int affine_splat_lds(R *d_I, const R *go, const R *A, const R *T, int nc, int64_
     pa.gate = gate;
     hipError_t e = bc ? launch_tiled<R, POS_AFFINE, true, false, 4>(d_I, nullptr, go, nullptr, pa, nc, tg, smem, nt, s)
                       : launch_tiled<R, POS_AFFINE, false, false, 4>(d_I, nullptr, go, nullptr, pa, nc, tg, smem, nt, s);
-    if (e != hipSuccess) return fail_hip(e, "affine_interp_backward (tiled splat)");
-    return finish_launch(s, "affine_interp_backward (tiled splat)");
+    return launched(e, s, "affine_interp_backward (tiled splat)");
 }
 
 // regrid_backward (cuda/affine.cu:767-855), 3D: every (n, c) plane of grad_out (source grid gs)
@@ -1019,8 +1017,7 @@ int regrid_splat_lds(R *d_I, const R *go, int64_t nplanes, const Geom &g, const 
         pa.S[d] = S[d];
     }
     hipError_t e = launch_tiled<R, POS_REGRID, false, false, 4>(d_I, nullptr, go, nullptr, pa, 1, tg, smem, nt, s);
-    if (e != hipSuccess) return fail_hip(e, "regrid_backward (tiled splat)");
-    return finish_launch(s, "regrid_backward (tiled splat)");
+    return launched(e, s, "regrid_backward (tiled splat)");
 }
 
 template int interp_backward_lds<float>(float *, float *, const float *, const float *, const float *, double, int,

@@ -931,19 +931,36 @@ def distance_transform(L, where="nonzero", label=0, spacing=1.0, squared=False):
     return out
 
 
-def _check_points(F, x, what, grad_out=None, backward=False):
-    """A field F (N or 1, C, *sp) with two or three spatial axes and a point set x (N, d, P), d = len(sp), of one
-    floating dtype (and, for the backward, grad_out (N, C, P)); returns (dim, nn, broadcast).  Every error of type,
-    dtype, shape, batch and contiguity is raised whatever device the tensors are on; the device checks come last."""
-    named = (("F", F), ("x", x)) + ((("grad_out", grad_out),) if backward else ())
+def _check_types(named):
+    """Every (name, tensor) pair is a tensor of one supported floating dtype, the first one's."""
     for name, t in named:
         if not isinstance(t, torch.Tensor):
             raise TypeError(f"{name} must be a torch.Tensor")
     for name, t in named:
         _suffix(t)
     for name, t in named[1:]:
-        if t.dtype != F.dtype:
-            raise RuntimeError(f"lagomorph_ext: dtype mismatch ({F.dtype} vs {t.dtype})")
+        if t.dtype != named[0][1].dtype:
+            raise RuntimeError(f"lagomorph_ext: dtype mismatch ({named[0][1].dtype} vs {t.dtype})")
+
+
+def _check_layout(named):
+    """Contiguity, then -- last, so that every other error is raised whatever device the tensors are on -- the devices."""
+    for name, t in named:
+        if not t.is_contiguous():
+            raise RuntimeError(f"{name} must be contiguous")
+    for name, t in named[1:]:
+        if t.device != named[0][1].device:
+            raise RuntimeError(f"lagomorph_ext: device mismatch ({named[0][1].device} vs {t.device})")
+    for name, t in named:
+        _check_input(t, name)
+
+
+def _check_points(F, x, what, grad_out=None, backward=False):
+    """A field F (N or 1, C, *sp) with two or three spatial axes and a point set x (N, d, P), d = len(sp), of one
+    floating dtype (and, for the backward, grad_out (N, C, P)); returns (dim, nn, broadcast).  Every error of type,
+    dtype, shape, batch and contiguity is raised whatever device the tensors are on; the device checks come last."""
+    named = (("F", F), ("x", x)) + ((("grad_out", grad_out),) if backward else ())
+    _check_types(named)
     dim = F.dim() - 2
     if dim not in (2, 3):
         raise RuntimeError(f"{what}: F must be a field of shape (N, C, *spatial) with two or three spatial axes, "
@@ -957,14 +974,7 @@ def _check_points(F, x, what, grad_out=None, backward=False):
     if backward and tuple(grad_out.shape) != (nn, F.size(1), x.size(2)):
         raise RuntimeError(f"{what}: grad_out of shape {tuple(grad_out.shape)} does not match the output "
                            f"{(nn, F.size(1), x.size(2))}")
-    for name, t in named:
-        if not t.is_contiguous():
-            raise RuntimeError(f"{name} must be contiguous")
-    for name, t in named[1:]:
-        if t.device != F.device:
-            raise RuntimeError(f"lagomorph_ext: device mismatch ({F.device} vs {t.device})")
-    for name, t in named:
-        _check_input(t, name)
+    _check_layout(named)
     return dim, nn, F.size(0) < nn
 
 
@@ -991,30 +1001,6 @@ def interp_points_backward(grad_out, F, x, need_F, need_x):
         _call("lago_interp_points_backward", F, _ptr(d_F), _ptr(d_x), _ptr(grad_out), _ptr(F), _ptr(x), dim, nn,
               F.size(1), x.size(2), nx, ny, nz, int(bc), int(bool(need_F)), int(bool(need_x)))
     return [d_F, d_x]
-
-
-def _check_types(named):
-    """Every (name, tensor) pair is a tensor of one supported floating dtype, the first one's."""
-    for name, t in named:
-        if not isinstance(t, torch.Tensor):
-            raise TypeError(f"{name} must be a torch.Tensor")
-    for name, t in named:
-        _suffix(t)
-    for name, t in named[1:]:
-        if t.dtype != named[0][1].dtype:
-            raise RuntimeError(f"lagomorph_ext: dtype mismatch ({named[0][1].dtype} vs {t.dtype})")
-
-
-def _check_layout(named):
-    """Contiguity, then -- last, so that every other error is raised whatever device the tensors are on -- the devices."""
-    for name, t in named:
-        if not t.is_contiguous():
-            raise RuntimeError(f"{name} must be contiguous")
-    for name, t in named[1:]:
-        if t.device != named[0][1].device:
-            raise RuntimeError(f"lagomorph_ext: device mismatch ({named[0][1].device} vs {t.device})")
-    for name, t in named:
-        _check_input(t, name)
 
 
 def bspline_prefilter(I, adjoint=False):
