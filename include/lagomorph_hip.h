@@ -65,6 +65,10 @@ extern "C" {
 #define LAGO_EDT_SURFACE 3
 #define LAGO_EDT_MAX_EXTENT 1024
 
+/* lago_field_energy, lago_field_energy_operator: which quadratic form of the field */
+#define LAGO_ENERGY_DIFFUSION 0
+#define LAGO_ENERGY_BENDING 1
+
 /* ---- housekeeping --------------------------------------------------------- */
 
 /* replaces set_debug_mode (extension.cpp:105-107): when non-zero every entry
@@ -507,7 +511,45 @@ long long lago_reversed_launches(void);
      * d_ctrl is not written).  No counterpart in the reference. */                                                  \
     int lago_ffd_expand_adjoint##SUF(REAL *d_ctrl, const REAL *grad_out, REAL *scratch, int64_t scratch_elems,       \
                                      int dim, int64_t rows, int64_t nx, int64_t ny, int64_t nz, int sx, int sy,      \
-                                     int sz, void *stream);
+                                     int sz, void *stream);                                                          \
+    /* lago_field_energy: the smoothness energy of a field, per batch item.  u: (nn, nc, nx, ny[, nz]), nc free      \
+     * (dim channels for a displacement, 1 for a bias field); energy: (nn); spacing: dim doubles h_a > 0, one per    \
+     * axis (host memory, read during the call).  V = the voxels of one item (not times nc); per item, summed over   \
+     * the channels k:                                                                                               \
+     *   LAGO_ENERGY_DIFFUSION  E = (1/V) sum_x sum_k sum_a (d_a u_k(x))^2,  d_a u(x) = (u(x + e_a) - u(x)) / h_a    \
+     *     where x_a + 1 < n_a and 0 otherwise (a forward difference with a Neumann border; an axis of extent 1      \
+     *     contributes nothing): VoxelMorph's penalty.                                                               \
+     *   LAGO_ENERGY_BENDING    E = (1/V) sum_x sum_k [ sum_a (d_aa u_k(x))^2 + 2 sum_{a<b} (d_ab u_k(x))^2 ],        \
+     *     d_aa u(x) = (u(x + e_a) - 2 u(x) + u(x - e_a)) / h_a^2 where 1 <= x_a <= n_a - 2 and 0 otherwise,         \
+     *     d_ab u(x) = (u(x + e_a + e_b) - u(x + e_a) - u(x + e_b) + u(x)) / (h_a h_b) where x_a + 1 < n_a and       \
+     *     x_b + 1 < n_b and 0 otherwise (forward-forward, so that d_ab^T d_ab = d_aa d_bb in the interior and the   \
+     *     operator there is exactly (sum_a d_aa)^2; axes of extent 1 or 2 drop their terms): Rueckert's, NiftyReg's \
+     *     and elastix's penalty.                                                                                    \
+     * Both are quadratic forms E = <u, A u> / V with A = sum_t w_t D_t^T D_t over the difference operators D_t      \
+     * above (weights 1 and 2), symmetric positive semidefinite, and dE/du = (2/V) A u exactly, at the borders too:  \
+     * lago_field_energy_operator.  Away from the borders A is -Laplacian (7-point) for diffusion and the discrete   \
+     * biharmonic operator (25-point in 3D, 13-point in 2D) for bending.                                             \
+     * The arithmetic of a voxel, its order (no fma) and its rounding count are csrc/energy_stencil.hpp; a float32   \
+     * operator value is within K 2^-24 |scale| sum |A| |u| of the exact one, K = 13 (bending), 8 (diffusion).       \
+     * Workgroups own voxel tiles of 8 x 8 x 64 (dim 2: 64 x 64) staged in LDS with their halo; every lane adds its  \
+     * voxels' terms, a tile's sum (added in double, fixed order) goes to `scratch` with a plain store               \
+     * (lago_field_energy_scratch_elems elements of REAL, need not be initialised, clobbered), and a second kernel   \
+     * adds one item's partials in double in a fixed order and writes E[n] in REAL.  4 bytes loaded per element      \
+     * (float32); no atomics: the same bits from call to call.  LAGO_ERR_INVALID before any device call: dim not 2   \
+     * or 3, an unknown kind, a negative extent, a plane of 2^29 elements or more, a null pointer, a spacing that is \
+     * not positive and finite, scratch_elems too small, energy or scratch overlapping u.  nn, nc or an extent equal \
+     * to 0: nothing is done (LAGO_OK; energy is not written).  No counterpart in the reference. */                  \
+    int lago_field_energy##SUF(REAL *energy, const REAL *u, REAL *scratch, int64_t scratch_elems, int kind, int dim,  \
+                               int64_t nn, int64_t nc, int64_t nx, int64_t ny, int64_t nz, const double *spacing,     \
+                               void *stream);                                                                        \
+    /* out[n] = scale[n] (A u)[n] with the A of lago_field_energy: out, u (nn, nc, sp); scale (nn) in device memory, \
+     * NULL for 1 (the backward of the energy passes 2 g_n / V without a host synchronisation or an extra pass).     \
+     * One load and one store per element, the halo of a tile (one voxel for diffusion, two for bending) from cache; \
+     * plain stores: the same bits from call to call.  LAGO_ERR_INVALID before any device call: as lago_field_energy \
+     * (no scratch), and out overlapping u or scale.  Empty problems: nothing is done (LAGO_OK). */                  \
+    int lago_field_energy_operator##SUF(REAL *out, const REAL *u, const REAL *scale, int kind, int dim, int64_t nn,   \
+                                        int64_t nc, int64_t nx, int64_t ny, int64_t nz, const double *spacing,        \
+                                        void *stream);
 
 LAGO_DECLARE(float, _f32)
 LAGO_DECLARE(double, _f64)
@@ -516,6 +558,11 @@ LAGO_DECLARE(double, _f64)
  * tile: rows x tiles x the control points a tile reaches); 0 for an empty problem, -1 for arguments the entry point
  * rejects.  The caller allocates.  No counterpart in the reference. */
 long long lago_ffd_scratch_elems(int dim, int64_t rows, int64_t nx, int64_t ny, int64_t nz, int sx, int sy, int sz);
+
+/* Elements of REAL that lago_field_energy needs as scratch for this problem (one partial sum per voxel tile: nn x nc x
+ * tiles of a plane); 0 for an empty problem, -1 for arguments the entry point rejects.  The caller allocates.  No
+ * counterpart in the reference. */
+long long lago_field_energy_scratch_elems(int kind, int dim, int64_t nn, int64_t nc, int64_t nx, int64_t ny, int64_t nz);
 
 /* How many scratch tables per row lago_mi_histogram can use for `rows` rows of `nvox` voxels at `bins` bins (>= 1: a
  * row is cut into chunks of a few thousand voxels, as many as keep the scratch of all rows within 8 MB).  The caller

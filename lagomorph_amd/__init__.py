@@ -28,6 +28,8 @@ if not _BUILDING:
     from .lddmm import EPDiff_step, LDDMMAtlasBuilder, expmap, expmap_advect, lddmm_step, shard_indices  # noqa: F401
     from .metric import FluidMetric, FluidMetricOperator, GaussianMetric, Metric  # noqa: F401
     from .points import InterpPointsFunction, deform_points, interp_points, landmark_distance  # noqa: F401
+    from .regularize import (EnergyOperatorFunction, FieldEnergyFunction, bending_energy, diffusion_energy,  # noqa: F401
+                             energy_operator, field_energy)
     from .similarity import (JointHistogramFunction, LNCCFunction, LNCCSimilarity, MISimilarity,  # noqa: F401
                              joint_histogram, lncc, lncc_loss, mi_loss, mutual_information)
     from .smooth import GaussianSmoothFunction, gaussian_smooth, gaussian_taps  # noqa: F401

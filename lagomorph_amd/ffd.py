@@ -5,6 +5,7 @@ model of a smooth multiplicative bias field.
 
     u = ffd_expand(c, I.shape[2:], spacing)        # (N, d, *sp), voxel units
     J = interp(I, u)                                # or interp_cubic; penalise folding with jacobian_determinant(u)
+    R = bending_energy(u)                           # Rueckert's smoothness penalty on the dense field (regularize.py)
 
 Lattice convention, per spatial axis with extent n and integer spacing s (in voxels, 1..32): the lattice has
 m = (n - 1) // s + 4 control points and point j sits at voxel (j - 1) s -- one point before the grid and at least two
@@ -15,7 +16,8 @@ t = (x % s) / s.  A lattice with c[j] = a (j - 1) s + b expands to a x + b; a co
 
 Fields are channel-first (N, C, *sp) with two or three spatial axes, float32 or float64, contiguous, on the GPU; C is
 free (d channels for a displacement, in voxel units as `interp` takes it; 1 for a scalar field).  No counterpart in the
-reference; no CPU path.
+reference; no CPU path.  `bending_energy(ffd_expand(c, shape, s))` penalises the dense field's second derivatives; its
+gradient reaches the lattice through `ffd_restrict`.
 """
 import torch
 

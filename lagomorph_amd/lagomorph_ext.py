@@ -89,6 +89,8 @@ _SIGS = {
     "lago_interp_bspline_backward": [_vp, _vp, _vp, _vp, _vp, _dbl, _int, _i64, _i64, _i64, _i64, _i64, _int, _int, _int, _vp],
     "lago_ffd_expand": [_vp, _vp, _int, _i64, _i64, _i64, _i64, _int, _int, _int, _vp],
     "lago_ffd_expand_adjoint": [_vp, _vp, _vp, _i64, _int, _i64, _i64, _i64, _i64, _int, _int, _int, _vp],
+    "lago_field_energy": [_vp, _vp, _vp, _i64, _int, _int, _i64, _i64, _i64, _i64, _i64, ctypes.POINTER(_dbl), _vp],
+    "lago_field_energy_operator": [_vp, _vp, _vp, _int, _int, _i64, _i64, _i64, _i64, _i64, ctypes.POINTER(_dbl), _vp],
     "lago_fluid_metric": [_vp, _vp, _vp, _i64, _int, _vp, _vp, _vp, _vp, _vp, _vp, _dbl, _dbl, _dbl, _int, _i64, _i64,
                           _i64, _i64, _vp],
     "lago_fluid_metric_scaled": [_vp, _vp, _vp, _i64, _int, _vp, _vp, _vp, _vp, _vp, _vp, _dbl, _dbl, _dbl, _int, _i64,
@@ -114,6 +116,8 @@ _lib.lago_distance_transform.argtypes = [_vp, _vp, _int, ctypes.c_int32, ctypes.
 _lib.lago_distance_transform.restype = _int
 _lib.lago_ffd_scratch_elems.argtypes = [_int, _i64, _i64, _i64, _i64, _int, _int, _int]
 _lib.lago_ffd_scratch_elems.restype = ctypes.c_longlong
+_lib.lago_field_energy_scratch_elems.argtypes = [_int, _int, _i64, _i64, _i64, _i64, _i64]
+_lib.lago_field_energy_scratch_elems.restype = ctypes.c_longlong
 
 
 class LagoTuning(ctypes.Structure):
