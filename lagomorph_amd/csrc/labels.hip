@@ -10,18 +10,16 @@
 //   warp_labels3_unroll_kernel the slab-interleaved walk of interp_fwd3_unroll_kernel (its reasons are in interp.hip):
 //                              U voxels a lane, every load and gather of a wave within ~256 contiguous bytes, the U * 4
 //                              pair gathers issued back to back.
-//   label_overlap_kernel       grid rows x chunks, the scheme of mi_hist_kernel: a workgroup walks its chunk of A and B
-//                              with 16-byte loads (scalar head and tail) and counts into a (K, 3) table of 32-bit
-//                              counters in LDS, one replica a wave while 64 KB hold them.  A wave first aggregates: the
-//                              lanes that hold the first pending lane's (a, b) pair are found with a ballot and ONE lane
-//                              adds their number (inside a structure the whole wave is one round, at a boundary two);
-//                              lanes still pending after two rounds add for themselves.  The partial table goes to the
-//                              slab (rows, chunks, K, 3) with plain stores; every slab entry is written.
-//   label_overlap_reduce_kernel sums the chunks of every entry into int64.
+//   label_overlap_kernel       the scheme of chunk_table.hpp in its wave-uniform form with 16-byte loads of A and B and a
+//                              (K, 3) table of 32-bit counters, one replica a wave while 64 KB hold them; the reducer
+//                              gives int64.  A wave first aggregates: the lanes that hold the first pending lane's
+//                              (a, b) pair are found with a ballot and ONE lane adds their number (inside a structure
+//                              the whole wave is one round, at a boundary two); lanes still pending after two rounds
+//                              add for themselves.
 //
 // No float atomic, no global atomic, no memset: both operators give the same bits from call to call, and the counts
 // are those of a sequential pass for any chunking.
-#include "common.hpp"
+#include "chunk_table.hpp"   // (and common.hpp)
 #include "label_vote.hpp"
 
 #ifndef LAGO_NT_LABELS_ST
@@ -198,21 +196,16 @@ static int warp_labels_impl(int32_t *out, const int32_t *L, const R *u, double d
 // ------------------------------------------------------------------ label_overlap
 
 constexpr int kLabChunkMin = LAGO_LABELS_CHUNK;   // voxels an overlap workgroup walks where the slab's cap allows
-constexpr int64_t kLabSlabBytes = 8ll << 20;   // the partial tables of all rows stay below this (or one table a row)
-constexpr size_t kLabLdsBytes = 64 * 1024;     // what the replicas of one workgroup may take
 
 struct OverlapArgs {
-    int K;
-    int rep;           // replicas of the table in LDS: 1, 2 or 4 (a wave adds into replica wave % rep)
-    uint32_t nvox;     // of one row
-    uint32_t chunks;   // workgroups per row
-    uint32_t chunk;    // voxels per workgroup
+    int K, rep;   // rep: replicas of the table in LDS, 1, 2 or 4 (a wave adds into replica wave % rep)
+    RowChunks rc;
 };
 
 extern __shared__ uint32_t lab_smem[];
 
 // One step of a wave: every lane with `valid` holds one voxel's pair (a, b).  Wave-uniform control flow throughout
-// (the callers' loops are): `todo` is a scalar mask.
+// (chunk_walk_uniform's loops are): `todo` is a scalar mask.
 __device__ __forceinline__ void overlap_add(uint32_t *tab, uint32_t K, bool valid, int32_t a, int32_t b) {
     const auto add = [&](int32_t x, int32_t y, uint32_t n) {
         if ((uint32_t)x < K) atomicAdd(tab + 3u * (uint32_t)x, n);
@@ -238,76 +231,27 @@ __global__ __launch_bounds__(kBlock) void label_overlap_kernel(uint32_t *__restr
     typedef int32_t vec __attribute__((ext_vector_type(4)));
     constexpr uint32_t VW = 4;
     const uint32_t K3 = 3u * (uint32_t)p.K;
-    for (uint32_t e = threadIdx.x; e < (uint32_t)p.rep * K3; e += kBlock) lab_smem[e] = 0u;
-    __syncthreads();
-    const uint32_t row = blockIdx.x / p.chunks, ch = blockIdx.x - row * p.chunks;   // uniform
-    const uint32_t c0 = ch * p.chunk;
-    const uint32_t n = c0 < p.nvox ? min(p.chunk, p.nvox - c0) : 0u;
-    const int32_t *Ar = A + (size_t)row * p.nvox + c0, *Br = B + (size_t)row * p.nvox + c0;
+    tables_zero(lab_smem, K3, p.rep);
+    const ChunkOfRow c = chunk_of_block(p.rc);
+    const int32_t *Ac = A + (size_t)c.row * p.rc.nvox + c.c0, *Bc = B + (size_t)c.row * p.rc.nvox + c.c0;   // of the chunk
     uint32_t *tab = lab_smem + ((threadIdx.x >> 6) & (uint32_t)(p.rep - 1)) * K3;
-    // a scalar head up to the first 16-byte boundary, vectors, a scalar tail; no vector where A and B are misaligned
-    // differently.  All three loops have uniform bounds: lanes past the end take part in overlap_add with valid = false.
-    const uint32_t mA = (uint32_t)(((uintptr_t)Ar / 4) % VW), mB = (uint32_t)(((uintptr_t)Br / 4) % VW);
-    const uint32_t head = mA == mB ? min((VW - mA) % VW, n) : n;
-    const uint32_t nvec = (n - head) / VW;
-    const uint32_t tail = head + nvec * VW;
-    const auto scalars = [&](uint32_t from, uint32_t to) {
-        for (uint32_t base = from; base < to; base += kBlock) {
-            const uint32_t i = base + threadIdx.x;
-            const bool valid = i < to;
-            overlap_add(tab, (uint32_t)p.K, valid, valid ? Ar[i] : 0, valid ? Br[i] : 0);
-        }
-    };
-    scalars(0, head);
-    for (uint32_t base = 0; base < nvec; base += kBlock) {
-        const uint32_t v = base + threadIdx.x;
-        const bool valid = v < nvec;
+    const uint32_t mA = misalign<VW>(Ac);
+    chunk_walk_uniform<VW>(c.n, mA == misalign<VW>(Bc), mA, [&](uint32_t i, bool valid) {
+        overlap_add(tab, (uint32_t)p.K, valid, valid ? Ac[i] : 0, valid ? Bc[i] : 0);
+    }, [&](uint32_t first, uint32_t i, bool valid) {
         vec x = {0, 0, 0, 0}, y = {0, 0, 0, 0};
         if (valid) {
-            x = *reinterpret_cast<const vec *>(Ar + head + v * VW);
-            y = *reinterpret_cast<const vec *>(Br + head + v * VW);
+            x = *reinterpret_cast<const vec *>(Ac + first + i);
+            y = *reinterpret_cast<const vec *>(Bc + first + i);
         }
 #pragma unroll
         for (uint32_t k = 0; k < VW; ++k) overlap_add(tab, (uint32_t)p.K, valid, x[k], y[k]);
-    }
-    scalars(tail, n);
-    __syncthreads();
-    uint32_t *o = slab + (size_t)blockIdx.x * K3;
-    for (uint32_t e = threadIdx.x; e < K3; e += kBlock) {
-        uint32_t sum = lab_smem[e];
-        for (int r = 1; r < p.rep; ++r) sum += lab_smem[(uint32_t)r * K3 + e];
-        o[e] = sum;
-    }
+    });
+    tables_store(slab, lab_smem, K3, p.rep);
 }
 
-// One workgroup per 64 entries of one row's (K, 3) table (the last group of a row is ragged where 3 K is no multiple of
-// 64), as mi_reduce_kernel: lane (part, e) sums the chunks part, part + 4, ... of its entry with eight loads in flight,
-// the four parts meet in LDS.  An integer sum: the order does not show.
-__global__ __launch_bounds__(kBlock) void label_overlap_reduce_kernel(long long *__restrict__ counts, const uint32_t *__restrict__ slab,
-                                                                      uint32_t chunks, uint32_t K3, uint32_t groups) {
-    __shared__ long long part[4][64];
-    const uint32_t row = blockIdx.x / groups, e = (blockIdx.x - row * groups) * 64 + (threadIdx.x & 63u);   // row: uniform
-    const uint32_t p = threadIdx.x >> 6;
-    long long sum = 0;
-    if (e < K3) {
-        const uint32_t *s = slab + (size_t)row * chunks * K3 + e;
-#pragma unroll 8
-        for (uint32_t c = p; c < chunks; c += 4) sum += (long long)s[(size_t)c * K3];
-    }
-    part[p][threadIdx.x & 63u] = sum;
-    __syncthreads();
-    if (p == 0 && e < K3) {
-        const uint32_t t = threadIdx.x;
-        counts[(size_t)row * K3 + e] = part[0][t] + part[1][t] + part[2][t] + part[3][t];
-    }
-}
-
-static int64_t overlap_chunks_wanted(int K, int64_t rows, int64_t nvox) {
-    const int64_t by_size = (nvox + kLabChunkMin - 1) / kLabChunkMin;
-    const int64_t cap = kLabSlabBytes / ((int64_t)K * 3 * 4) / (rows > 1 ? rows : 1);
-    const int64_t c = by_size < cap ? by_size : cap;
-    return c < 1 ? 1 : c;
-}
+// what table_reduce_kernel does with a finished sum: stored as it is
+struct CountFinish { long long *counts; __device__ void operator()(size_t i, long long sum) const { counts[i] = sum; } };
 
 static int label_overlap_impl(long long *counts, const int32_t *A, const int32_t *B, uint32_t *scratch, int64_t scratch_chunks,
                               int K, int64_t rows, int64_t nvox, void *stream) {
@@ -316,41 +260,27 @@ static int label_overlap_impl(long long *counts, const int32_t *A, const int32_t
     if (nvox > (1ll << 30)) return fail_invalid("label_overlap: more than 2^30 voxels in a row");
     if (rows == 0) return LAGO_OK;
     if (!counts || !scratch || (nvox && (!A || !B))) return fail_invalid("label_overlap: null pointer");
-    if (scratch_chunks < 1) return fail_invalid("label_overlap: scratch must hold at least one table per row");
+    const uint32_t K3 = 3u * (uint32_t)K;
     OverlapArgs p;
     p.K = K;
-    p.nvox = (uint32_t)nvox;
-    {   // chunks per row and voxels per chunk (a multiple of four, no chunk empty unless the row is)
-        int64_t c = overlap_chunks_wanted(K, rows, nvox);
-        c = c < scratch_chunks ? c : scratch_chunks;
-        int64_t per = (nvox + c - 1) / c;
-        per = (per + 3) / 4 * 4;
-        p.chunk = (uint32_t)per;
-        p.chunks = per ? (uint32_t)((nvox + per - 1) / per) : 1u;
-    }
-    const uint32_t K3 = 3u * (uint32_t)K;
-    const auto fits = [&](int r) { return (size_t)r * K3 * 4 <= kLabLdsBytes; };
+    size_t sbytes;
+    if (const int rc = plan_tables<uint32_t>(p.rc, sbytes, "label_overlap", K3, rows, nvox, kLabChunkMin, scratch_chunks); rc != kLaunchNow)
+        return rc;
+    const auto fits = [&](int r) { return (size_t)r * K3 * 4 <= kTableLdsBytes; };
     p.rep = fits(4) ? 4 : (fits(2) ? 2 : 1);   // K <= 1365 four, K <= 2730 two, else one (4096 labels: 48 KB)
-    const uint64_t nb = (uint64_t)rows * p.chunks;
-    const uint32_t groups = (K3 + 63) / 64;   // of the reducer
-    if (nb >= (1ull << 31) || (uint64_t)rows * groups >= (1ull << 31)) return fail_invalid("label_overlap: bad extent");
-    const size_t ibytes = (size_t)rows * p.nvox * 4, sbytes = (size_t)nb * K3 * 4, cbytes = (size_t)rows * K3 * 8;
+    const size_t ibytes = (size_t)rows * nvox * 4, cbytes = (size_t)rows * K3 * 8;
     if (any_overlap({{counts, cbytes}, {scratch, sbytes}}, {{A, ibytes}, {B, ibytes}}))
         return fail_invalid("label_overlap: counts and scratch must not overlap an input or each other");
     hipStream_t s = (hipStream_t)stream;
-    hipError_t e = launch(label_overlap_kernel, dim3((uint32_t)nb), dim3(kBlock), (size_t)p.rep * K3 * 4, s, scratch, A, B, p);
-    if (e != hipSuccess) return fail_hip(e, "label_overlap");
-    e = launch(label_overlap_reduce_kernel, dim3((uint32_t)rows * groups), dim3(kBlock), 0, s, counts, (const uint32_t *)scratch,
-               p.chunks, K3, groups);
-    return launched(e, s, "label_overlap");
+    const hipError_t e = launch(label_overlap_kernel, dim3((uint32_t)rows * p.rc.chunks), dim3(kBlock), (size_t)p.rep * K3 * 4, s, scratch, A, B, p);
+    return reduce_tables("label_overlap", e, s, p.rc, rows, K3, (const uint32_t *)scratch, CountFinish{counts});
 }
 
 }  // namespace lago
 
 extern "C" {
 int lago_label_overlap_scratch_chunks(int num_labels, int64_t rows, int64_t nvox) {
-    if (num_labels < 1 || num_labels > LAGO_LABELS_MAX || rows < 0 || nvox < 0 || nvox > (1ll << 30)) return 1;
-    return (int)lago::overlap_chunks_wanted(num_labels, rows, nvox);
+    return lago::scratch_chunks(num_labels >= 1 && num_labels <= LAGO_LABELS_MAX, (int64_t)num_labels * 12, rows, nvox, lago::kLabChunkMin);
 }
 int lago_label_overlap(long long *counts, const int32_t *A, const int32_t *B, uint32_t *scratch, int64_t scratch_chunks,
                        int num_labels, int64_t rows, int64_t nvox, void *stream) {

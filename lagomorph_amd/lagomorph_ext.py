@@ -755,7 +755,7 @@ def mi_range(r, name):
 def mi_histogram(I, J, bins, range_I, range_J):
     """The Parzen-window joint histogram P (N, C, bins, bins), float64, of I and J (N, C, *sp) over the ranges
     (lo, hi) of the two images: cubic B-spline windows on both, summed as 64-bit fixed-point integers, so that P has
-    the same bits from call to call (csrc/mi.hip: mi_hist_kernel, mi_reduce_kernel; the definition is in
+    the same bits from call to call (csrc/mi.hip: mi_hist_kernel, csrc/chunk_table.hpp: table_reduce_kernel; the definition is in
     include/lagomorph_hip.h).  The scratch of partial tables is allocated here.  Not in the reference; no CPU path."""
     dim, nx, ny, nz, bins, (loI, hiI), (loJ, hiJ) = _check_mi(I, J, bins, range_I, range_J)
     rows, nvox = I.size(0) * I.size(1), nx * ny * nz
@@ -860,7 +860,7 @@ def label_overlap(A, B, num_labels):
     """int64 counts (N, K, 3) of two label maps A, B (N, 1, *sp): per item and label k in [0, K = num_labels)
     [#(A == k), #(B == k), #(A == k and B == k)]; a voxel whose label is outside [0, K) counts in nothing for that
     image.  Integer sums in LDS tables and a slab of partial tables allocated here, no atomic on memory: the same
-    bits from call to call (csrc/labels.hip: label_overlap_kernel, label_overlap_reduce_kernel).  Labels go to the
+    bits from call to call (csrc/labels.hip: label_overlap_kernel, csrc/chunk_table.hpp: table_reduce_kernel).  Labels go to the
     call as int32 (see warp_labels).  Not in the reference; no CPU path."""
     K = label_count(num_labels)
     _check_labels(A, "A")

@@ -139,6 +139,49 @@ def test_label_overlap_at_odd_pointer_offsets(offs):
         assert torch.equal(got.cpu(), torch.from_numpy(ref.overlap(A.reshape((N, 1) + sp), B.reshape((N, 1) + sp), K))), sp
 
 
+def _overlap_with_scratch(A, B, K, chunks):
+    """lago_label_overlap with a scratch of `chunks` partial tables a row, as lagomorph_ext.label_overlap calls it."""
+    from lagomorph_amd import lagomorph_ext as ext
+
+    rows, nvox = A.size(0), A[0].numel()
+    counts = torch.full((rows, K, 3), -1, dtype=torch.int64, device=A.device)
+    scratch = torch.empty((rows * chunks * K * 3,), dtype=torch.int32, device=A.device)
+    ext._launch(ext._lib.lago_label_overlap, A, ext._ptr(counts), ext._ptr(A), ext._ptr(B), ext._ptr(scratch), chunks, K, rows, nvox)
+    return counts
+
+
+@pytest.mark.parametrize("K", [5, 200, 4096])
+@pytest.mark.parametrize("sp", [(27, 25, 25), (131, 127)], ids=str)
+def test_two_ragged_chunks_a_row_equal_one_chunk_a_row(sp, K):
+    """16875 voxels are chunks of 8440 + 8435, 16637 of 8320 + 8317 (csrc/chunk_table.hpp); the rows are odd, so rows 1
+    and 2 start off the 16-byte boundary.  Labels outside [0, K) and negative ones among them.  The counts equal the
+    reference, and so does the same call with a scratch of ONE table a row (one workgroup walks the row)."""
+    import lagomorph_amd as lm
+    from lagomorph_amd import lagomorph_ext as ext
+
+    rows, nvox = 3, int(np.prod(sp))
+    assert nvox % 2 == 1 and ext.label_overlap_chunks(K, rows, nvox) == 2
+    rng = np.random.default_rng([K, *sp])
+    A = rng.integers(-3, K + 3, (rows, 1) + sp).astype(np.int32)
+    B = np.where(rng.random(A.shape) < 0.5, A, rng.integers(-3, K + 3, A.shape)).astype(np.int32)
+    A.reshape(-1)[:3] = (-2 ** 31, 2 ** 31 - 1, K)
+    Ad, Bd = _dev(A), _dev(B)
+    got = lm.label_overlap(Ad, Bd, K)
+    assert torch.equal(got.cpu(), torch.from_numpy(ref.overlap(A, B, K)))
+    assert torch.equal(_overlap_with_scratch(Ad, Bd, K, 1), got)
+
+
+@pytest.mark.parametrize("sp", [(1, 1), (1, 5), (3, 3, 3), (1, 259)], ids=str)
+def test_label_overlap_of_the_smallest_rows(sp):
+    """Rows below one vector, below one workgroup of lanes, and of a vector count that is no multiple of 256 with a tail:
+    every lane takes part in the wave's ballots whether it holds a voxel or not."""
+    import lagomorph_amd as lm
+
+    K, rng = 3, np.random.default_rng([3, *sp])
+    A, B = (rng.integers(-1, K + 1, (N, 1) + sp).astype(np.int32) for _ in range(2))
+    assert torch.equal(lm.label_overlap(_dev(A), _dev(B), K).cpu(), torch.from_numpy(ref.overlap(A, B, K)))
+
+
 def test_label_overlap_dtypes():
     import lagomorph_amd as lm
 

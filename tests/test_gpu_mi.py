@@ -1,4 +1,4 @@
-"""GPU: joint_histogram (csrc/mi.hip: mi_hist_kernel, mi_reduce_kernel), its backward (mi_bwd_kernel),
+"""GPU: joint_histogram (csrc/mi.hip: mi_hist_kernel; csrc/chunk_table.hpp: table_reduce_kernel), its backward (mi_bwd_kernel),
 mutual_information, mi_loss, MISimilarity and the latter as the `similarity` of lddmm_step and LDDMMAtlasBuilder.
 
 P is compared with the numpy reference tests/mi_ref.py (held against central differences and against the kernels' own
@@ -387,3 +387,62 @@ def test_production_size_128(lm):
     u = [units_of(a, b, torch.float32) for a, b in zip((mi, dI, dJ), (rmi, rdI, rdJ))]
     print(f"{shape} B={B}: MI {u[0]:.3f} dI {u[1]:.3f} dJ {u[2]:.3f} x RTOL x max|ref|")
     assert max(u) <= 1.0, u
+
+
+# ---- 10. the chunking does not show (csrc/chunk_table.hpp)
+
+_CHUNK_REFS = {}
+
+
+def _chunk_case(lead, sp, B):
+    """(I, J, range_I, range_J, P) of a noise pair in float32 values, the reference computed once for both precisions."""
+    key = (lead, sp, B)
+    if key not in _CHUNK_REFS:
+        rng = np.random.default_rng([B, *sp])
+        Ih, Nh = (rng.standard_normal(lead + sp).astype(np.float32) for _ in range(2))
+        Jh = (np.float32(0.8) * Ih + np.float32(0.6) * Nh).astype(np.float32)
+        rI, rJ = (-2.0, 2.0), (-1.5, 2.5)   # both clamp a few voxels
+        P = mi_ref.joint_histogram(Ih.astype(np.float64), Jh.astype(np.float64), B, rI, rJ)
+        P.setflags(write=False)
+        _CHUNK_REFS[key] = (Ih, Jh, rI, rJ, P)
+    return _CHUNK_REFS[key]
+
+
+def _histogram_with_scratch(I, J, B, rI, rJ, tables):
+    """lago_mi_histogram with a scratch of `tables` partial tables a row, as lagomorph_ext.mi_histogram calls it."""
+    from lagomorph_amd import lagomorph_ext as ext
+
+    dim, nx, ny, nz = ext._spatial(I)
+    rows = I.size(0) * I.size(1)
+    P = torch.full((I.size(0), I.size(1), B, B), -1.0, dtype=torch.float64, device=I.device)
+    scratch = torch.empty((rows * tables * B * B,), dtype=torch.int64, device=I.device)
+    ext._call("lago_mi_histogram", I, ext._ptr(P), ext._ptr(I), ext._ptr(J), ext._ptr(scratch), tables, B, *rI, *rJ, dim,
+              rows, nx, ny, nz)
+    return P
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("B", [4, 32, 64])
+@pytest.mark.parametrize("sp", [(17, 19, 13), (67, 63)], ids=str)
+def test_two_ragged_chunks_a_row_equal_one_chunk_a_row(lm, dtype, B, sp):
+    """4199 voxels are chunks of 2100 + 2099, 4221 of 2112 + 2109; the rows are odd, so rows 1 and 2 start off the
+    16-byte boundary and walk a scalar head, vectors and a scalar tail.  P equals the reference integer for integer,
+    and so does the same call with a scratch of ONE table a row (fewer than wanted: one workgroup walks the row)."""
+    from lagomorph_amd import lagomorph_ext as ext
+
+    lead, nvox = (1, 3), int(np.prod(sp))
+    assert nvox % 2 == 1 and ext._lib.lago_mi_scratch_tables(B, 3, nvox) == 2
+    Ih, Jh, rI, rJ, want = _chunk_case(lead, sp, B)
+    I, J = dev(Ih, dtype), dev(Jh, dtype)
+    P = lm.joint_histogram(I, J, bins=B, range_I=rI, range_J=rJ)
+    assert torch.equal(P.cpu(), torch.from_numpy(want))
+    assert torch.equal(_histogram_with_scratch(I, J, B, rI, rJ, 1), P)
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("sp", [(1, 1), (1, 5), (3, 3, 3), (1, 259)], ids=str)
+def test_the_smallest_rows(lm, dtype, sp):
+    """Rows below one vector, below one workgroup of lanes, and of a vector count that is no multiple of 256 with a tail."""
+    Ih, Jh, rI, rJ, want = _chunk_case((1, 2), sp, 4)
+    P = lm.joint_histogram(dev(Ih, dtype), dev(Jh, dtype), bins=4, range_I=rI, range_J=rJ)
+    assert torch.equal(P.cpu(), torch.from_numpy(want))
