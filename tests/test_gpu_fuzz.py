@@ -81,3 +81,29 @@ def test_a_constructed_cell_face_event_is_found_and_proved():
     assert any(f"voxel {x0}" in ln for ln in lines), lines
     assert max(ev["after"].values()) <= 1e-5, ev
     assert ev["after"]["m"] <= ev["before"]["m"], ev
+
+
+def _newer_families():
+    import fuzz_ops_cases
+
+    return fuzz_ops_cases.FAMILIES
+
+
+@pytest.mark.parametrize("family", _newer_families())
+def test_random_cases_of_the_newer_operators(family):
+    """tools/fuzz_ops.py on a FIXED number of cases from a fixed seed (tests/fuzz_ops_cases.py: COUNTS, SEED -- the cases
+    whose gate coverage tests/test_fuzz_ops_host.py checks), so that a failure reproduces: every case judged by its
+    family's own rule, a second call after one launch, one batch item alone, and every third case under the sibling
+    kernels.  `python tools/fuzz_ops.py --case FAMILY SEED INDEX` replays a mismatch; profiles/fuzz_ops.md has the
+    counts, the times and the long form's totals."""
+    import fuzz_ops
+    import fuzz_ops_cases
+
+    try:
+        counts, worst = fuzz_ops.run(families=(family,), cases=fuzz_ops_cases.COUNTS[family], seed=fuzz_ops_cases.SEED)
+    except SystemExit as e:   # the tool reports a mismatch this way
+        pytest.fail(str(e))
+    print(fuzz_ops.report(counts, worst))
+    assert counts[family]["unjudged"] == {}, counts[family]["unjudged"]
+    assert counts[family]["judged"] == fuzz_ops_cases.COUNTS[family]
+    assert all(v <= 1.0 for v in worst[family].values()), worst[family]

@@ -68,12 +68,8 @@ def host(t):
 
 
 def units_of(got, want, dtype, scale=None):
-    """max |got - want| in units of RTOL x max|want| (or x scale)."""
-    got, want = host(got).astype(np.float64), np.asarray(want, dtype=np.float64)
-    assert got.shape == want.shape, f"shape {got.shape} vs {want.shape}"
-    ref = np.abs(want).max() if scale is None else scale
-    err = np.abs(got - want).max() if got.size else 0.0
-    return err / (RTOL[dtype] * max(ref, 1e-300))
+    """max |got - want| in units of RTOL x max|want| (or x scale): gauss_ref.units, which tests/fuzz_ops_cases.py shares."""
+    return gauss_ref.units(host(got), want, NPDT[dtype], scale)
 
 
 def same_values(a, b):
