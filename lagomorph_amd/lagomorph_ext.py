@@ -96,28 +96,6 @@ _SIGS = {
     "lago_fluid_metric_scaled": [_vp, _vp, _vp, _i64, _int, _vp, _vp, _vp, _vp, _vp, _vp, _dbl, _dbl, _dbl, _int, _i64,
                                  _i64, _i64, _i64, _dbl, _vp],
 }
-_fn = {}
-for _name, _args in _SIGS.items():
-    for _suf in ("_f32", "_f64"):
-        _f = getattr(_lib, _name + _suf, None)
-        if _f is None:
-            continue
-        _f.argtypes = _args
-        _f.restype = _int
-        _fn[_name + _suf] = _f
-_lib.lago_set_debug.argtypes = [_int]
-_lib.lago_mi_scratch_tables.argtypes = [_int, _i64, _i64]
-_lib.lago_mi_scratch_tables.restype = _int
-_lib.lago_label_overlap.argtypes = [_vp, _vp, _vp, _vp, _i64, _int, _i64, _i64, _vp]
-_lib.lago_label_overlap.restype = _int
-_lib.lago_label_overlap_scratch_chunks.argtypes = [_int, _i64, _i64]
-_lib.lago_label_overlap_scratch_chunks.restype = _int
-_lib.lago_distance_transform.argtypes = [_vp, _vp, _int, ctypes.c_int32, ctypes.POINTER(_dbl), _int, _int, _i64, _i64, _i64, _i64, _vp]
-_lib.lago_distance_transform.restype = _int
-_lib.lago_ffd_scratch_elems.argtypes = [_int, _i64, _i64, _i64, _i64, _int, _int, _int]
-_lib.lago_ffd_scratch_elems.restype = ctypes.c_longlong
-_lib.lago_field_energy_scratch_elems.argtypes = [_int, _int, _i64, _i64, _i64, _i64, _i64]
-_lib.lago_field_energy_scratch_elems.restype = ctypes.c_longlong
 
 
 class LagoTuning(ctypes.Structure):
@@ -130,12 +108,33 @@ class LagoTuning(ctypes.Structure):
                 ("fluid_xpass_persist", ctypes.c_int32), ("affine_box", ctypes.c_int32), ("compose_near", ctypes.c_int32)]
 
 
-_lib.lago_get_tuning.argtypes = [ctypes.POINTER(LagoTuning)]
-_lib.lago_get_tuning.restype = None
-_lib.lago_default_tuning.argtypes = [ctypes.POINTER(LagoTuning)]
-_lib.lago_default_tuning.restype = None
-_lib.lago_set_tuning.argtypes = [ctypes.POINTER(LagoTuning)]
-_lib.lago_set_tuning.restype = _int
+# (argtypes, restype) of the symbols without a precision suffix: scratch queries, the integer-label kernels, counters, tuning
+_PLAIN_SIGS = {
+    "lago_set_debug": ([_int], _int),
+    "lago_mi_scratch_tables": ([_int, _i64, _i64], _int),
+    "lago_label_overlap": ([_vp, _vp, _vp, _vp, _i64, _int, _i64, _i64, _vp], _int),
+    "lago_label_overlap_scratch_chunks": ([_int, _i64, _i64], _int),
+    "lago_distance_transform": ([_vp, _vp, _int, ctypes.c_int32, ctypes.POINTER(_dbl), _int, _int, _i64, _i64, _i64, _i64,
+                                 _vp], _int),
+    "lago_ffd_scratch_elems": ([_int, _i64, _i64, _i64, _i64, _int, _int, _int], ctypes.c_longlong),
+    "lago_field_energy_scratch_elems": ([_int, _int, _i64, _i64, _i64, _i64, _i64], ctypes.c_longlong),
+    "lago_get_tuning": ([ctypes.POINTER(LagoTuning)], None),
+    "lago_default_tuning": ([ctypes.POINTER(LagoTuning)], None),
+    "lago_set_tuning": ([ctypes.POINTER(LagoTuning)], _int),
+    "lago_path_launches": ([_int], ctypes.c_longlong),
+    "lago_reversed_launches": ([], ctypes.c_longlong),
+}
+_fn = {}   # the typed entry points _call dispatches on; the unsuffixed symbols are reached as _lib.<name>
+for _name, _args in _SIGS.items():
+    for _suf in ("_f32", "_f64"):
+        _f = getattr(_lib, _name + _suf, None)
+        if _f is None:
+            continue
+        _f.argtypes, _f.restype = _args, _int
+        _fn[_name + _suf] = _f
+for _name, (_args, _res) in _PLAIN_SIGS.items():
+    _f = getattr(_lib, _name)   # a library without one of these fails here, at import
+    _f.argtypes, _f.restype = _args, _res
 _tune_lock = threading.Lock()
 
 
@@ -189,8 +188,28 @@ def _suffix(t):
     raise RuntimeError(f"lagomorph_ext: only float32 and float64 are supported (got {t.dtype})")
 
 
+# ---------------------------------------------------------------------------
+# The argument frame: one function per decision an entry point takes before its launch.  An entry point is a sequence
+# of these calls, and the order of its calls is the order in which it reports errors.  Two orders are in use:
+#   device first  the reference's surface (interp, jtv, affine, regrid, fluid_operator) and the fused kernels beside
+#                 it (compose, lincomb, Ad_star, ad_star, mi): _check_input on each tensor, as the reference's
+#                 CHECK_INPUT did, then _same -- through _check_inputs, or written out where one tensor is checked,
+#                 something stands between the two steps (mi, lincomb) or the call is timed as launch latency
+#                 (interp, affine)
+#   device last   the newer families (gauss, lncc, invert, labels, edt, points, bspline, ffd, energy): _check_types,
+#                 the family's shape checks, then _check_layout or _check_cuda, so that every other error shows on a
+#                 CPU tensor too
+# Nothing here reads a tensor's values: shapes, dtypes, devices, strides and data_ptr() only.
+
+
+def _check_tensors(named):
+    for name, t in named:
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"{name} must be a torch.Tensor")
+
+
 def _check_input(x, name):
-    # CHECK_INPUT, extension.cpp:8-10
+    # CHECK_INPUT, extension.cpp:8-10 (on the path of every call: the type check is written out, not a _check_tensors call)
     if not isinstance(x, torch.Tensor):
         raise TypeError(f"{name} must be a torch.Tensor")
     if not x.is_cuda:
@@ -207,6 +226,42 @@ def _same(ref, *others):
             raise RuntimeError(f"lagomorph_ext: device mismatch ({ref.device} vs {o.device})")
 
 
+def _check_inputs(named):
+    """Device first: every (name, tensor) pair passes CHECK_INPUT, then all share the first one's dtype and device."""
+    for name, t in named:
+        _check_input(t, name)
+    _same(named[0][1], *[t for _, t in named[1:]])
+
+
+def _check_types(named):
+    """Every (name, tensor) pair is a tensor of one supported floating dtype, the first one's."""
+    _check_tensors(named)
+    for name, t in named:
+        _suffix(t)
+    for name, t in named[1:]:
+        if t.dtype != named[0][1].dtype:
+            raise RuntimeError(f"lagomorph_ext: dtype mismatch ({named[0][1].dtype} vs {t.dtype})")
+
+
+def _check_layout(named):
+    """Contiguity, then -- last, so that every other error is raised whatever device the tensors are on -- the devices."""
+    for name, t in named:
+        if not t.is_contiguous():
+            raise RuntimeError(f"{name} must be contiguous")
+    for name, t in named[1:]:
+        if t.device != named[0][1].device:
+            raise RuntimeError(f"lagomorph_ext: device mismatch ({named[0][1].device} vs {t.device})")
+    for name, t in named:
+        _check_input(t, name)
+
+
+def _check_cuda(named):
+    """The device check of the entry points that make their inputs contiguous themselves."""
+    for name, t in named:
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise RuntimeError(f"{name} must be a CUDA tensor")
+
+
 def _spatial(t):
     d = t.dim() - 2
     if d == 2:
@@ -214,6 +269,67 @@ def _spatial(t):
     if d == 3:
         return 3, t.size(2), t.size(3), t.size(4)
     return d, 0, 0, 0
+
+
+def _spatial_frame(t, message):
+    """(dim, nx, ny, nz) of a channel-first tensor (N, C, *sp) as the C side takes them: the family's error unless it has
+    two or three spatial axes."""
+    frame = _spatial(t)
+    if frame[0] not in (2, 3):
+        raise RuntimeError(message)
+    return frame
+
+
+def _pad(values, fill, n=3):
+    """Per-axis values (extents, spacings, origins, LUT pointers) as the n arguments the C call takes, unused axes as `fill`."""
+    values = tuple(values)
+    return values + (fill,) * (n - len(values))
+
+
+def _broadcast(field, nn, message, empty=False):
+    """Is `field`, of nn items or of one, broadcast over a batch of nn?  RuntimeError(message) for any other pair of batch
+    sizes.  One item against an empty batch is an error on the reference's surface and passes with `empty` (the newer
+    families, which accept a batch size in (1, nn))."""
+    n = field.size(0)
+    if n != nn and (n != 1 or (nn == 0 and not empty)):
+        raise RuntimeError(message)
+    return n < nn
+
+
+def _on_grid(u, I, dim):
+    """Is u a vector field on I's grid: `dim` channels and I's spatial shape?"""
+    return u.size(1) == dim and tuple(u.shape[2:]) == tuple(I.shape[2:])
+
+
+def _overlaps(a, b):
+    """Do the byte ranges of two contiguous tensors intersect?  (a partially overlapping view counts: the kernel
+    gathers from its inputs while it writes `out`)"""
+    a0, b0 = a.data_ptr(), b.data_ptr()
+    return a.numel() > 0 and b.numel() > 0 and a0 < b0 + b.numel() * b.element_size() and b0 < a0 + a.numel() * a.element_size()
+
+
+def _check_dest(out, name, ref, message, *inputs):
+    """A caller-supplied destination: a contiguous device tensor of ref's dtype and device, then RuntimeError(message)
+    unless it has ref's shape and its bytes overlap none of `inputs`."""
+    _check_input(out, name)
+    _same(ref, out)
+    if out.shape != ref.shape or any(_overlaps(out, x) for x in inputs):
+        raise RuntimeError(message)
+
+
+def _scratch_elems(query, *args):
+    """The scratch size a `*_scratch_elems` query of the library gives; its error when the arguments do not fit."""
+    elems = int(query(*args))
+    if elems < 0:
+        raise RuntimeError(_lib.lago_last_error().decode("utf-8", "replace"))
+    return elems
+
+
+def _env_flag(name):
+    """A profiling variable of the environment: None when unset, else whether it is switched on (parsed defensively: an
+    empty or odd value must not break `import lagomorph_amd`)."""
+    v = os.environ.get(name)
+    return None if v is None else v.strip().lower() not in ("", "0", "off", "false", "no")
 
 
 def _call(name, ref, *args):
@@ -289,15 +405,9 @@ def set_stencil_tile(on):
     tune(stencil_tile=on)
 
 
-_lib.lago_path_launches.restype = ctypes.c_longlong
-_lib.lago_path_launches.argtypes = [_int]
 PATHS = ("gather_window", "stencil_tile", "vector_gather", "splat_shear", "splat_shear_mc", "splat_tiled", "splat_global",
          "fluid_lds", "fluid_2d", "fluid_xpass", "fluid_rocfft", "splat_2d", "splat_affine_box", "fluid_generic",
          "gather_window_near")  # LAGO_PATH_* of include/lagomorph_hip.h, in order
-
-
-_lib.lago_reversed_launches.restype = ctypes.c_longlong
-_lib.lago_reversed_launches.argtypes = []
 
 
 def reversed_launches():
@@ -324,13 +434,12 @@ def set_compose_near(on):
     tune(compose_near=1 if on else 0)
 
 
-if os.environ.get("LAGO_GATHER_WINDOW") is not None:  # profiling convenience: A/B under rocprofv3 without code changes
-    # (parsed defensively: an empty or odd value of a profiling variable must not break `import lagomorph_amd`)
-    set_gather_window(os.environ["LAGO_GATHER_WINDOW"].strip().lower() not in ("", "0", "off", "false", "no"))
+if _env_flag("LAGO_GATHER_WINDOW") is not None:  # profiling convenience: A/B under rocprofv3 without code changes
+    set_gather_window(_env_flag("LAGO_GATHER_WINDOW"))
 
 
-if os.environ.get("LAGO_COMPOSE_NEAR") is not None:  # the same convenience for the near-identity arm of compose
-    set_compose_near(os.environ["LAGO_COMPOSE_NEAR"].strip().lower() not in ("", "0", "off", "false", "no"))
+if _env_flag("LAGO_COMPOSE_NEAR") is not None:  # the same convenience for the near-identity arm of compose
+    set_compose_near(_env_flag("LAGO_COMPOSE_NEAR"))
 
 
 def set_vector_kernels(on):
@@ -355,36 +464,33 @@ def interp_forward(Iv, u, dt=1.0):
     _check_input(Iv, "Iv")
     _check_input(u, "u")
     _same(Iv, u)
-    dim, nx, ny, nz = _spatial(Iv)
-    if dim not in (2, 3):
-        raise RuntimeError("Only two- and three-dimensional interpolation is supported")
-    if u.dim() != Iv.dim() or u.size(1) != dim or tuple(u.shape[2:]) != tuple(Iv.shape[2:]):
+    dim, nx, ny, nz = _spatial_frame(Iv, "Only two- and three-dimensional interpolation is supported")
+    if u.dim() != Iv.dim() or not _on_grid(u, Iv, dim):
         raise RuntimeError(f"interp_forward: displacement of shape {tuple(u.shape)} does not match image {tuple(Iv.shape)}")
-    nn = max(u.size(0), Iv.size(0))
-    bc = Iv.size(0) < nn
-    if (bc and Iv.size(0) != 1) or u.size(0) != nn:
-        raise RuntimeError("interp_forward: batch sizes of I and u are incompatible")
+    nn = u.size(0)
+    bc = _broadcast(Iv, nn, "interp_forward: batch sizes of I and u are incompatible")
     out = torch.empty((nn, Iv.size(1)) + tuple(Iv.shape[2:]), dtype=Iv.dtype, device=Iv.device)
     _call("lago_interp_forward", Iv, _ptr(out), _ptr(Iv), _ptr(u), float(dt), dim, nn, Iv.size(1), nx, ny, nz, int(bc))
     return out
 
 
-def interp_backward(grad_out, I, u, dt, need_I, need_u):
-    """extension.cpp:145-156 -> cuda/interp.cu:246-313.  Returns [d_I, d_u]; both always allocated."""
+def _interp_backward_args(grad_out, I, u):
+    """The argument block interp_backward and interp_backward_fused share: (dim, nx, ny, nz, nn, broadcast)."""
     _check_input(grad_out, "grad_out")
     _check_input(I, "I")
     _check_input(u, "u")
     _same(I, u, grad_out)
-    dim, nx, ny, nz = _spatial(I)
-    if dim not in (2, 3):
-        raise RuntimeError("Only two- and three-dimensional interpolation is supported")
-    nn = max(u.size(0), I.size(0))
-    bc = I.size(0) < nn
-    if (bc and I.size(0) != 1) or u.size(0) != nn:
-        raise RuntimeError("interp_backward: batch sizes of I and u are incompatible")
-    if (tuple(grad_out.shape) != (nn, I.size(1)) + tuple(I.shape[2:]) or u.dim() != I.dim() or u.size(1) != dim
-            or tuple(u.shape[2:]) != tuple(I.shape[2:])):
+    dim, nx, ny, nz = _spatial_frame(I, "Only two- and three-dimensional interpolation is supported")
+    nn = u.size(0)
+    bc = _broadcast(I, nn, "interp_backward: batch sizes of I and u are incompatible")
+    if tuple(grad_out.shape) != (nn, I.size(1)) + tuple(I.shape[2:]) or u.dim() != I.dim() or not _on_grid(u, I, dim):
         raise RuntimeError("interp_backward: grad_out / I / u shapes are inconsistent")
+    return dim, nx, ny, nz, nn, bc
+
+
+def interp_backward(grad_out, I, u, dt, need_I, need_u):
+    """extension.cpp:145-156 -> cuda/interp.cu:246-313.  Returns [d_I, d_u]; both always allocated."""
+    dim, nx, ny, nz, nn, bc = _interp_backward_args(grad_out, I, u)
     d_I = torch.empty_like(I)
     d_u = torch.empty_like(u)
     _call("lago_interp_backward", I, _ptr(d_I), _ptr(d_u), _ptr(grad_out), _ptr(I), _ptr(u), float(dt), dim, nn,
@@ -394,9 +500,7 @@ def interp_backward(grad_out, I, u, dt, need_I, need_u):
 
 def interp_hessian_diagonal_image(Iv, u, dt):
     """cuda/interp.cu:351-381 (2D only; accumulates into plane 0 like the reference)."""
-    _check_input(Iv, "Iv")
-    _check_input(u, "u")
-    _same(Iv, u)
+    _check_inputs((("Iv", Iv), ("u", u)))
     if Iv.dim() != 4 or u.dim() != 4 or u.size(1) != 2:
         raise RuntimeError("interp_hessian_diagonal_image is only implemented for two-dimensional images")
     nn = max(u.size(0), Iv.size(0))
@@ -406,10 +510,12 @@ def interp_hessian_diagonal_image(Iv, u, dt):
     return out
 
 
+_JTV_DIMS = "Only two- and three-dimensional jacobian times vectorfield is supported"
+
+
 def _check_jtv(g, v):
-    for x, nm in ((g, "g"), (v, "v")):
-        if not isinstance(x, torch.Tensor) or not x.is_cuda:
-            raise RuntimeError(f"{nm} must be a CUDA tensor")
+    """A pair of the jtv family, which makes its inputs contiguous itself (the second of any pair reports as "v")."""
+    _check_cuda((("g", g), ("v", v)))
     _same(g, v)
 
 
@@ -417,12 +523,10 @@ def jacobian_times_vectorfield_forward(g, v, displacement, transpose):
     """cuda/diff.cu:129-185: (Dg + [displacement] I) v, or its transpose."""
     _check_jtv(g, v)
     g, v = g.contiguous(), v.contiguous()
-    dim, nx, ny, nz = _spatial(g)
-    if dim not in (2, 3):
-        raise RuntimeError("Only two- and three-dimensional jacobian times vectorfield is supported")
+    dim, nx, ny, nz = _spatial_frame(g, _JTV_DIMS)
     if g.size(0) != v.size(0):
         raise RuntimeError("arguments must have same batch size dimension")
-    if v.size(1) != dim or tuple(v.shape[2:]) != tuple(g.shape[2:]):
+    if not _on_grid(v, g, dim):
         raise RuntimeError("vector field is of wrong dimension")
     out = torch.empty_like(g)
     _call("lago_jtv_forward", g, _ptr(out), _ptr(g), _ptr(v), int(bool(displacement)), int(bool(transpose)), dim,
@@ -436,19 +540,14 @@ def jacobian_times_vectorfield_backward(grad_out, v, w, displacement, transpose,
     _check_jtv(v, w)
     _check_jtv(v, grad_out)
     grad_out, v, w = grad_out.contiguous(), v.contiguous(), w.contiguous()
-    dim, nx, ny, nz = _spatial(v)
-    if dim not in (2, 3):
-        raise RuntimeError("Only two- and three-dimensional jacobian times vectorfield is supported")
+    dim, nx, ny, nz = _spatial_frame(v, _JTV_DIMS)
     if v.size(0) != w.size(0):
         raise RuntimeError("arguments must have same batch size dimension")
-    if w.size(1) != dim or tuple(w.shape[2:]) != tuple(v.shape[2:]) or grad_out.shape != v.shape:
+    if not _on_grid(w, v, dim) or grad_out.shape != v.shape:
         raise RuntimeError("vector field is of wrong dimension")
     d_w = torch.empty_like(w)
     if d_v is not None:
-        _check_input(d_v, "d_v")
-        _same(v, d_v)
-        if d_v.shape != v.shape:
-            raise RuntimeError("jacobian_times_vectorfield_backward: d_v must have the shape of v")
+        _check_dest(d_v, "d_v", v, "jacobian_times_vectorfield_backward: d_v must have the shape of v")
         _call("lago_jtv_backward_acc", v, _ptr(d_v), _ptr(d_w), _ptr(grad_out), _ptr(v), _ptr(w), int(bool(displacement)),
               int(bool(transpose)), dim, v.size(0), v.size(1), nx, ny, nz, 1)
         return [d_v, d_w]
@@ -462,10 +561,8 @@ def jacobian_times_vectorfield_adjoint_forward(g, v):
     """cuda/diff.cu:634-672"""
     _check_jtv(g, v)
     g, v = g.contiguous(), v.contiguous()
-    dim, nx, ny, nz = _spatial(g)
-    if dim not in (2, 3):
-        raise RuntimeError("Only two- and three-dimensional jacobian times vectorfield is supported")
-    if v.size(1) != dim or v.size(0) != g.size(0) or tuple(v.shape[2:]) != tuple(g.shape[2:]):
+    dim, nx, ny, nz = _spatial_frame(g, _JTV_DIMS)
+    if not _on_grid(v, g, dim) or v.size(0) != g.size(0):
         raise RuntimeError("vector field is of wrong dimension")
     out = torch.empty_like(g)
     _call("lago_jtv_adjoint_forward", g, _ptr(out), _ptr(g), _ptr(v), dim, g.size(0), g.size(1), nx, ny, nz)
@@ -477,9 +574,7 @@ def jacobian_times_vectorfield_adjoint_backward(grad_out, v, w, need_v, need_w):
     _check_jtv(v, w)
     _check_jtv(v, grad_out)
     grad_out, v, w = grad_out.contiguous(), v.contiguous(), w.contiguous()
-    dim, nx, ny, nz = _spatial(v)
-    if dim not in (2, 3):
-        raise RuntimeError("Only two- and three-dimensional jacobian times vectorfield is supported")
+    dim, nx, ny, nz = _spatial_frame(v, _JTV_DIMS)
     if w.size(1) != dim or v.size(1) != dim or v.shape != w.shape or grad_out.shape != v.shape:
         raise RuntimeError("vector field is of wrong dimension")
     d_v, d_w = torch.empty_like(v), torch.empty_like(w)
@@ -489,12 +584,9 @@ def jacobian_times_vectorfield_adjoint_backward(grad_out, v, w, need_v, need_w):
 
 
 def _check_jacdet(u):
-    if not isinstance(u, torch.Tensor) or not u.is_cuda:
-        raise RuntimeError("u must be a CUDA tensor")
+    _check_cuda((("u", u),))
     _suffix(u)
-    dim, nx, ny, nz = _spatial(u)
-    if dim not in (2, 3):
-        raise RuntimeError("Only two- and three-dimensional jacobian determinant is supported")
+    dim, nx, ny, nz = _spatial_frame(u, "Only two- and three-dimensional jacobian determinant is supported")
     if u.size(1) != dim:
         raise RuntimeError("jacobian determinant is only defined for vector fields")
     return dim, nx, ny, nz
@@ -525,17 +617,12 @@ def jacobian_determinant_backward(grad_out, u, displacement):
 
 
 def _check_invert(u, name="u"):
-    if not isinstance(u, torch.Tensor):
-        raise TypeError(f"{name} must be a torch.Tensor")
-    _suffix(u)
-    dim, nx, ny, nz = _spatial(u)
-    if dim not in (2, 3):
-        raise RuntimeError("Only two- and three-dimensional displacement inversion is supported")
+    _check_types(((name, u),))
+    dim, nx, ny, nz = _spatial_frame(u, "Only two- and three-dimensional displacement inversion is supported")
     if u.size(1) != dim:
         raise RuntimeError(f"invert_displacement: {name} must be a vector field (N, d, *spatial) with d = len(spatial), "
                            f"got {tuple(u.shape)}")
-    if not u.is_cuda:
-        raise RuntimeError(f"{name} must be a CUDA tensor")
+    _check_cuda(((name, u),))
     return dim, nx, ny, nz
 
 
@@ -569,6 +656,7 @@ def invert_displacement_adjoint(grad_out, u, v):
 
 GAUSS_MAX_RADIUS = 32   # LAGO_GAUSS_MAX_RADIUS of include/lagomorph_hip.h
 GAUSS_MODES = {"wrap": 0, "zero": 1}   # LAGO_GAUSS_WRAP / LAGO_GAUSS_ZERO
+_GAUSS_DIMS = "Only two- and three-dimensional gaussian smoothing is supported"   # smooth._plan raises it too
 
 
 def gaussian_smooth_forward(x, radii, taps, mode, alpha=1.0, out=None, accumulate=False):
@@ -577,25 +665,17 @@ def gaussian_smooth_forward(x, radii, taps, mode, alpha=1.0, out=None, accumulat
     (ignored where r == 0); mode "wrap" or "zero".  The result is `out` when given (like x, not overlapping it), a new
     tensor otherwise.  One scratch tensor like x is allocated here when two or more axes are filtered.  Not in the
     reference; no CPU path."""
-    if not isinstance(x, torch.Tensor):
-        raise TypeError("x must be a torch.Tensor")
-    _suffix(x)
-    dim, nx, ny, nz = _spatial(x)
-    if dim not in (2, 3):
-        raise RuntimeError("Only two- and three-dimensional gaussian smoothing is supported")
+    _check_types((("x", x),))
+    dim, nx, ny, nz = _spatial_frame(x, _GAUSS_DIMS)
     radii, half = _gauss_half_taps("gaussian_smooth", dim, radii, taps, mode)
     if accumulate and out is None:
         raise RuntimeError("gaussian_smooth: accumulate needs out")
-    if not x.is_cuda:
-        raise RuntimeError("x must be a CUDA tensor")
+    _check_cuda((("x", x),))
     x = x.contiguous()
     if out is None:
         out = torch.empty_like(x)
     else:
-        _check_input(out, "out")
-        _same(x, out)
-        if out.shape != x.shape:
-            raise RuntimeError("gaussian_smooth: out must have the shape of x")
+        _check_dest(out, "out", x, "gaussian_smooth: out must have the shape of x")
         if _overlaps(out, x):
             raise RuntimeError("gaussian_smooth: out must not overlap x")
     scratch = torch.empty_like(x) if sum(r > 0 for r in radii) >= 2 else None
@@ -613,10 +693,15 @@ def gaussian_smooth_forward(x, radii, taps, mode, alpha=1.0, out=None, accumulat
     return out
 
 
-def _gauss_half_taps(what, dim, radii, taps, mode):
-    """The mode / radius / tap checks of the entry point `what`: (radii as ints, the half-tap block lago_gauss_smooth takes)."""
+def _gauss_mode(what, mode):
     if mode not in GAUSS_MODES:
         raise ValueError(f"{what}: unknown mode {mode!r} (one of {sorted(GAUSS_MODES)})")
+    return GAUSS_MODES[mode]
+
+
+def _gauss_half_taps(what, dim, radii, taps, mode):
+    """The mode / radius / tap checks of the entry point `what`: (radii as ints, the half-tap block lago_gauss_smooth takes)."""
+    _gauss_mode(what, mode)
     radii = [int(r) for r in radii]
     if len(radii) != dim or len(taps) != dim:
         raise ValueError(f"{what}: {dim} radii and tap vectors are needed, one per spatial axis")
@@ -635,18 +720,19 @@ def _gauss_half_taps(what, dim, radii, taps, mode):
     return radii, half
 
 
-def _check_lncc_pair(I, J):
-    for x, nm in ((I, "I"), (J, "J")):
-        if not isinstance(x, torch.Tensor):
-            raise TypeError(f"{nm} must be a torch.Tensor")
-    _suffix(I)
-    dim, nx, ny, nz = _spatial(I)
-    if dim not in (2, 3):
-        raise RuntimeError("Only two- and three-dimensional lncc is supported")
+def _check_same_shape(I, J, what):
+    """The image pair of a similarity (`what`: "lncc" or "mutual_information"), here and in similarity.py."""
     if J.shape != I.shape:
-        raise RuntimeError(f"lncc: I {tuple(I.shape)} and J {tuple(J.shape)} must have the same shape")
+        raise RuntimeError(f"{what}: I {tuple(I.shape)} and J {tuple(J.shape)} must have the same shape")
+
+
+def _check_lncc_pair(I, J):
+    _check_tensors((("I", I), ("J", J)))
+    _suffix(I)
+    frame = _spatial_frame(I, "Only two- and three-dimensional lncc is supported")
+    _check_same_shape(I, J, "lncc")
     _same(I, J)
-    return dim, nx, ny, nz
+    return frame
 
 
 def _check_lncc_eps(eps):
@@ -663,8 +749,7 @@ def lncc_moments(I, J, radii, taps, mode):
     when an axis besides the last is filtered.  Not in the reference; no CPU path."""
     dim, nx, ny, nz = _check_lncc_pair(I, J)
     radii, half = _gauss_half_taps("lncc", dim, radii, taps, mode)
-    if not I.is_cuda:
-        raise RuntimeError("I must be a CUDA tensor")
+    _check_cuda((("I", I),))
     I, J = I.contiguous(), J.contiguous()
     out = torch.empty((5,) + tuple(I.shape), dtype=I.dtype, device=I.device)
     scratch = torch.empty_like(out) if any(r > 0 for r in radii[:-1]) else None
@@ -676,9 +761,7 @@ def lncc_moments(I, J, radii, taps, mode):
 
 def lncc_cc(moments, eps):
     """cc = sX^2 / (sI sJ + eps) (N, C, *sp) from the moments of lncc_moments (csrc/lncc.hip: lncc_cc_kernel)."""
-    if not isinstance(moments, torch.Tensor):
-        raise TypeError("moments must be a torch.Tensor")
-    _suffix(moments)
+    _check_types((("moments", moments),))
     if moments.dim() not in (5, 6) or moments.size(0) != 5:
         raise RuntimeError(f"lncc_cc: moments must be (5, N, C, *spatial), got {tuple(moments.shape)}")
     eps = _check_lncc_eps(eps)
@@ -702,8 +785,7 @@ def lncc_backward(grad_out, I, J, moments, radii, taps, mode, eps, need_I=True, 
     _same(I, grad_out, moments)
     if not (need_I or need_J):
         return None, None
-    if not I.is_cuda:
-        raise RuntimeError("I must be a CUDA tensor")
+    _check_cuda((("I", I),))
     I, J, grad_out, moments = I.contiguous(), J.contiguous(), grad_out.contiguous(), moments.contiguous()
     which = (1 if need_I else 0) | (2 if need_J else 0)
     k = 5 if which == 3 else 3
@@ -727,12 +809,9 @@ def _check_mi(I, J, bins, range_I, range_J):
     _check_input(J, "J")
     _suffix(I)
     _same(I, J)
-    dim, nx, ny, nz = _spatial(I)
-    if dim not in (2, 3):
-        raise RuntimeError("Only two- and three-dimensional mutual information is supported")
-    if J.shape != I.shape:
-        raise RuntimeError(f"mutual_information: I {tuple(I.shape)} and J {tuple(J.shape)} must have the same shape")
-    return (dim, nx, ny, nz, mi_bins(bins), mi_range(range_I, "range_I"), mi_range(range_J, "range_J"))
+    frame = _spatial_frame(I, "Only two- and three-dimensional mutual information is supported")
+    _check_same_shape(I, J, "mutual_information")
+    return (*frame, mi_bins(bins), mi_range(range_I, "range_I"), mi_range(range_J, "range_J"))
 
 
 def mi_bins(bins):
@@ -808,8 +887,7 @@ def label_count(num_labels):
 def _check_labels(x, name):
     """A label map (N, 1, *sp) of an integer dtype; the device checks come last (_check_input), so that every error of
     shape, dtype, mode or label count is raised whatever device the tensors are on."""
-    if not isinstance(x, torch.Tensor):
-        raise TypeError(f"{name} must be a torch.Tensor")
+    _check_tensors(((name, x),))
     if x.dtype not in _LABEL_DTYPES:
         raise RuntimeError(f"{name} must hold integer labels (uint8, int16, int32 or int64), got dtype {x.dtype}")
     if x.dim() not in (4, 5) or x.size(1) != 1:
@@ -830,21 +908,16 @@ def warp_labels(L, u, dt=1.0, mode="vote"):
     checked: that would synchronise).  Not differentiable.  Not in the reference; no CPU path."""
     mode = label_mode(mode)
     _check_labels(L, "L")
-    if not isinstance(u, torch.Tensor):
-        raise TypeError("u must be a torch.Tensor")
-    _suffix(u)
-    dim = L.dim() - 2
-    if u.dim() != L.dim() or u.size(1) != dim or tuple(u.shape[2:]) != tuple(L.shape[2:]):
+    _check_types((("u", u),))
+    dim, nx, ny, nz = _spatial(L)
+    if u.dim() != L.dim() or not _on_grid(u, L, dim):
         raise RuntimeError(f"warp_labels: displacement of shape {tuple(u.shape)} does not match labels {tuple(L.shape)}")
     nn = u.size(0)
-    if L.size(0) not in (1, nn):
-        raise RuntimeError("warp_labels: batch sizes of L and u are incompatible")
+    bc = _broadcast(L, nn, "warp_labels: batch sizes of L and u are incompatible", empty=True)
     if L.device != u.device:
         raise RuntimeError(f"lagomorph_ext: device mismatch ({L.device} vs {u.device})")
     _check_input(L, "L")
     _check_input(u, "u")
-    bc = L.size(0) < nn
-    _, nx, ny, nz = _spatial(L)
     L32 = _as_int32(L)
     out = torch.empty((nn, 1) + tuple(L.shape[2:]), dtype=torch.int32, device=L.device)
     _call("lago_warp_labels", u, _ptr(out), _ptr(L32), _ptr(u), float(dt), mode, int(bc), dim, nn, nx, ny, nz)
@@ -911,8 +984,7 @@ def distance_transform(L, where="nonzero", label=0, spacing=1.0, squared=False):
     "surface" of `label`); the definition is in include/lagomorph_hip.h (csrc/edt.hip: edt_pass_kernel, one launch per
     axis, no scratch buffer).  The call takes int32 (see warp_labels).  Not in the reference; no CPU path."""
     where = edt_where(where)
-    if not isinstance(L, torch.Tensor):
-        raise TypeError("L must be a torch.Tensor")
+    _check_tensors((("L", L),))
     if L.dtype != torch.bool:
         _check_labels(L, "L")
     elif L.dim() not in (4, 5) or L.size(1) != 1:
@@ -935,59 +1007,31 @@ def distance_transform(L, where="nonzero", label=0, spacing=1.0, squared=False):
     return out
 
 
-def _check_types(named):
-    """Every (name, tensor) pair is a tensor of one supported floating dtype, the first one's."""
-    for name, t in named:
-        if not isinstance(t, torch.Tensor):
-            raise TypeError(f"{name} must be a torch.Tensor")
-    for name, t in named:
-        _suffix(t)
-    for name, t in named[1:]:
-        if t.dtype != named[0][1].dtype:
-            raise RuntimeError(f"lagomorph_ext: dtype mismatch ({named[0][1].dtype} vs {t.dtype})")
-
-
-def _check_layout(named):
-    """Contiguity, then -- last, so that every other error is raised whatever device the tensors are on -- the devices."""
-    for name, t in named:
-        if not t.is_contiguous():
-            raise RuntimeError(f"{name} must be contiguous")
-    for name, t in named[1:]:
-        if t.device != named[0][1].device:
-            raise RuntimeError(f"lagomorph_ext: device mismatch ({named[0][1].device} vs {t.device})")
-    for name, t in named:
-        _check_input(t, name)
-
-
 def _check_points(F, x, what, grad_out=None, backward=False):
     """A field F (N or 1, C, *sp) with two or three spatial axes and a point set x (N, d, P), d = len(sp), of one
-    floating dtype (and, for the backward, grad_out (N, C, P)); returns (dim, nn, broadcast).  Every error of type,
+    floating dtype (and, for the backward, grad_out (N, C, P)); returns (dim, nx, ny, nz, nn, broadcast).  Every error of type,
     dtype, shape, batch and contiguity is raised whatever device the tensors are on; the device checks come last."""
     named = (("F", F), ("x", x)) + ((("grad_out", grad_out),) if backward else ())
     _check_types(named)
-    dim = F.dim() - 2
-    if dim not in (2, 3):
-        raise RuntimeError(f"{what}: F must be a field of shape (N, C, *spatial) with two or three spatial axes, "
-                           f"got shape {tuple(F.shape)}")
+    dim, nx, ny, nz = _spatial_frame(F, f"{what}: F must be a field of shape (N, C, *spatial) with two or three spatial "
+                                        f"axes, got shape {tuple(F.shape)}")
     if x.dim() != 3 or x.size(1) != dim:
         raise RuntimeError(f"{what}: x must be a point set of shape (N, {dim}, P) for a field with {dim} spatial axes, "
                            f"got shape {tuple(x.shape)}")
     nn = x.size(0)
-    if F.size(0) not in (1, nn):
-        raise RuntimeError(f"{what}: batch sizes of F ({F.size(0)}) and x ({nn}) are incompatible")
+    bc = _broadcast(F, nn, f"{what}: batch sizes of F ({F.size(0)}) and x ({nn}) are incompatible", empty=True)
     if backward and tuple(grad_out.shape) != (nn, F.size(1), x.size(2)):
         raise RuntimeError(f"{what}: grad_out of shape {tuple(grad_out.shape)} does not match the output "
                            f"{(nn, F.size(1), x.size(2))}")
     _check_layout(named)
-    return dim, nn, F.size(0) < nn
+    return dim, nx, ny, nz, nn, bc
 
 
 def interp_points_forward(F, x):
     """out (N, C, P): F (N or 1, C, *sp) sampled multilinearly at the positions x (N, d, P), in voxel-index units;
     lago_interp_points of include/lagomorph_hip.h (csrc/points.hip: interp_points_fwd_kernel).  Not in the reference;
     no CPU path."""
-    dim, nn, bc = _check_points(F, x, "interp_points")
-    _, nx, ny, nz = _spatial(F)
+    dim, nx, ny, nz, nn, bc = _check_points(F, x, "interp_points")
     out = torch.empty((nn, F.size(1), x.size(2)), dtype=F.dtype, device=F.device)
     _call("lago_interp_points", F, _ptr(out), _ptr(F), _ptr(x), dim, nn, F.size(1), x.size(2), nx, ny, nz, int(bc))
     return out
@@ -997,8 +1041,7 @@ def interp_points_backward(grad_out, F, x, need_F, need_x):
     """[d_F like F or None, d_x like x or None] for grad_out (N, C, P): lago_interp_points_backward
     (csrc/points.hip: interp_points_bwd_kernel).  A gradient that is not needed is not computed.  d_F is a sum of
     hardware float atomics (its last bits differ from call to call), d_x repeats bit for bit."""
-    dim, nn, bc = _check_points(F, x, "interp_points_backward", grad_out, backward=True)
-    _, nx, ny, nz = _spatial(F)
+    dim, nx, ny, nz, nn, bc = _check_points(F, x, "interp_points_backward", grad_out, backward=True)
     d_F = torch.empty_like(F) if need_F else None
     d_x = torch.empty_like(x) if need_x else None
     if need_F or need_x:
@@ -1011,10 +1054,8 @@ def bspline_prefilter(I, adjoint=False):
     """Cubic B-spline coefficients (N, C, *sp) of the samples I (N, C, *sp), mirror border; adjoint: the transposed
     operator.  lago_bspline_prefilter of include/lagomorph_hip.h (csrc/bspline.hip).  Not in the reference; no CPU path."""
     _check_types((("I", I),))
-    dim, nx, ny, nz = _spatial(I)
-    if dim not in (2, 3):
-        raise RuntimeError(f"bspline_prefilter: I must be a field of shape (N, C, *spatial) with two or three spatial axes, "
-                           f"got shape {tuple(I.shape)}")
+    dim, nx, ny, nz = _spatial_frame(I, "bspline_prefilter: I must be a field of shape (N, C, *spatial) with two or three "
+                                        f"spatial axes, got shape {tuple(I.shape)}")
     _check_layout((("I", I),))
     out = torch.empty_like(I)
     _call("lago_bspline_prefilter", I, _ptr(out), _ptr(I), int(bool(adjoint)), dim, I.size(0) * I.size(1), nx, ny, nz)
@@ -1023,31 +1064,27 @@ def bspline_prefilter(I, adjoint=False):
 
 def _check_bspline(C, u, what, grad_out=None):
     """Coefficients C (N or 1, K, *sp) with two or three spatial axes and a displacement u (N, d, *sp) of one floating
-    dtype (and, for the backward, grad_out (N, K, *sp)); returns (dim, nn, broadcast).  Every error of type, dtype,
-    shape, batch and contiguity is raised whatever device the tensors are on; the device checks come last."""
+    dtype (and, for the backward, grad_out (N, K, *sp)); returns (dim, nx, ny, nz, nn, broadcast).  Every error of type,
+    dtype, shape, batch and contiguity is raised whatever device the tensors are on; the device checks come last."""
     named = (("C", C), ("u", u)) + ((("grad_out", grad_out),) if grad_out is not None else ())
     _check_types(named)
-    dim = C.dim() - 2
-    if dim not in (2, 3):
-        raise RuntimeError(f"{what}: C must be a field of shape (N, K, *spatial) with two or three spatial axes, "
-                           f"got shape {tuple(C.shape)}")
-    if u.dim() != C.dim() or u.size(1) != dim or tuple(u.shape[2:]) != tuple(C.shape[2:]):
+    dim, nx, ny, nz = _spatial_frame(C, f"{what}: C must be a field of shape (N, K, *spatial) with two or three spatial "
+                                        f"axes, got shape {tuple(C.shape)}")
+    if u.dim() != C.dim() or not _on_grid(u, C, dim):
         raise RuntimeError(f"{what}: displacement of shape {tuple(u.shape)} does not match the field {tuple(C.shape)}")
     nn = u.size(0)
-    if C.size(0) not in (1, nn):
-        raise RuntimeError(f"{what}: batch sizes of C ({C.size(0)}) and u ({nn}) are incompatible")
+    bc = _broadcast(C, nn, f"{what}: batch sizes of C ({C.size(0)}) and u ({nn}) are incompatible", empty=True)
     if grad_out is not None and tuple(grad_out.shape) != (nn, C.size(1)) + tuple(C.shape[2:]):
         raise RuntimeError(f"{what}: grad_out of shape {tuple(grad_out.shape)} does not match the output "
                            f"{(nn, C.size(1)) + tuple(C.shape[2:])}")
     _check_layout(named)
-    return dim, nn, C.size(0) < nn
+    return dim, nx, ny, nz, nn, bc
 
 
 def interp_bspline_forward(C, u, dt=1.0):
     """out (N, K, *sp): the cubic B-spline with coefficients C (N or 1, K, *sp) at i + dt u(i); lago_interp_bspline
     (csrc/bspline.hip: interp_bspline_fwd_kernel).  Not in the reference; no CPU path."""
-    dim, nn, bc = _check_bspline(C, u, "interp_bspline")
-    _, nx, ny, nz = _spatial(C)
+    dim, nx, ny, nz, nn, bc = _check_bspline(C, u, "interp_bspline")
     out = torch.empty((nn, C.size(1)) + tuple(C.shape[2:]), dtype=C.dtype, device=C.device)
     _call("lago_interp_bspline", C, _ptr(out), _ptr(C), _ptr(u), float(dt), dim, nn, C.size(1), nx, ny, nz, int(bc))
     return out
@@ -1057,8 +1094,7 @@ def interp_bspline_backward(grad_out, C, u, dt, need_C, need_u):
     """[d_C like C or None, d_u like u or None] for grad_out (N, K, *sp): lago_interp_bspline_backward
     (csrc/bspline.hip: interp_bspline_bwd_kernel).  A gradient that is not needed is not computed.  d_C is a sum of
     hardware float atomics (its last bits differ from call to call), d_u repeats bit for bit."""
-    dim, nn, bc = _check_bspline(C, u, "interp_bspline_backward", grad_out)
-    _, nx, ny, nz = _spatial(C)
+    dim, nx, ny, nz, nn, bc = _check_bspline(C, u, "interp_bspline_backward", grad_out)
     d_C = torch.empty_like(C) if need_C else None
     d_u = torch.empty_like(u) if need_u else None
     if need_C or need_u:
@@ -1102,10 +1138,8 @@ def _check_ffd(x, shape, spacing, what):
     raised whatever device the tensor is on; the device checks come last."""
     name = "ctrl" if shape is not None else "g"
     _check_types(((name, x),))
-    dim = x.dim() - 2
-    if dim not in (2, 3):
-        raise RuntimeError(f"{what}: {name} must be a field of shape (N, C, *spatial) with two or three spatial axes, "
-                           f"got shape {tuple(x.shape)}")
+    dim = _spatial_frame(x, f"{what}: {name} must be a field of shape (N, C, *spatial) with two or three spatial axes, "
+                            f"got shape {tuple(x.shape)}")[0]
     if shape is None:
         shape = tuple(x.shape[2:])
         if min(shape) < 1:
@@ -1126,18 +1160,13 @@ def _check_ffd(x, shape, spacing, what):
     return dim, shape, sp
 
 
-def _ffd_args(dim, shape, sp):
-    return (dim,), tuple(shape) + (1,) * (3 - dim), tuple(sp) + (1,) * (3 - dim)
-
-
 def ffd_expand(ctrl, shape, spacing):
     """out (N, C, *shape): the control lattice ctrl (N, C, *ffd_grid_shape(shape, spacing)) expanded by its uniform
     cubic B-spline; lago_ffd_expand of include/lagomorph_hip.h (csrc/ffd.hip: ffd_expand_kernel).  No atomics: the
     same bits from call to call.  Not in the reference; no CPU path."""
     dim, shape, sp = _check_ffd(ctrl, shape, spacing, "ffd_expand")
     out = torch.empty(tuple(ctrl.shape[:2]) + shape, dtype=ctrl.dtype, device=ctrl.device)
-    (d,), n, s = _ffd_args(dim, shape, sp)
-    _call("lago_ffd_expand", ctrl, _ptr(out), _ptr(ctrl), d, ctrl.size(0) * ctrl.size(1), *n, *s)
+    _call("lago_ffd_expand", ctrl, _ptr(out), _ptr(ctrl), dim, ctrl.size(0) * ctrl.size(1), *_pad(shape, 1), *_pad(sp, 1))
     return out
 
 
@@ -1149,13 +1178,25 @@ def ffd_expand_adjoint(g, spacing):
     dim, shape, sp = _check_ffd(g, None, spacing, "ffd_expand_adjoint")
     rows = g.size(0) * g.size(1)
     d_ctrl = torch.empty(tuple(g.shape[:2]) + ffd_grid_shape(shape, sp), dtype=g.dtype, device=g.device)
-    (d,), n, s = _ffd_args(dim, shape, sp)
-    elems = int(_lib.lago_ffd_scratch_elems(d, rows, *n, *s))
-    if elems < 0:
-        raise RuntimeError(_lib.lago_last_error().decode("utf-8", "replace"))
+    n, s = _pad(shape, 1), _pad(sp, 1)
+    elems = _scratch_elems(_lib.lago_ffd_scratch_elems, dim, rows, *n, *s)
     scratch = torch.empty((elems,), dtype=g.dtype, device=g.device)
-    _call("lago_ffd_expand_adjoint", g, _ptr(d_ctrl), _ptr(g), _ptr(scratch), elems, d, rows, *n, *s)
+    _call("lago_ffd_expand_adjoint", g, _ptr(d_ctrl), _ptr(g), _ptr(scratch), elems, dim, rows, *n, *s)
     return d_ctrl
+
+
+def _check_luts(what, ref, cosluts, sinluts, lengths):
+    """The cosine and sine LUT of every axis, of ref's dtype and device and of that axis's length in `lengths`, made
+    contiguous: [cos 0, sin 0, cos 1, ...] (the caller keeps the list alive over its launch)."""
+    luts = []
+    for d, n in enumerate(lengths):
+        for t in (cosluts[d], sinluts[d]):
+            if t.dtype != ref.dtype:
+                raise RuntimeError("Type of LUTs must equal that of image")
+            if not t.is_cuda or t.device != ref.device or t.numel() != n:
+                raise RuntimeError(f"{what}: LUT on wrong device or of wrong length")
+            luts.append(t.contiguous())
+    return luts
 
 
 def fluid_operator(Fmv, inverse, cosluts, sinluts, alpha, beta, gamma):
@@ -1170,18 +1211,10 @@ def fluid_operator(Fmv, inverse, cosluts, sinluts, alpha, beta, gamma):
         raise RuntimeError("Only two- and three-dimensional fluid metric is supported")
     if Fmv.size(1) != dim or Fmv.size(-1) != 2:
         raise RuntimeError("Vector field has incorrect shape for dimension")
-    luts = []
-    for d in range(dim):
-        for t in (cosluts[d], sinluts[d]):
-            if t.dtype != Fmv.dtype:
-                raise RuntimeError("Type of LUTs must equal that of image")
-            if not t.is_cuda or t.device != Fmv.device or t.numel() != Fmv.size(2 + d):
-                raise RuntimeError("fluid_operator: LUT on wrong device or of wrong length")
-            luts.append(t.contiguous())
-    sh = [Fmv.size(2 + d) for d in range(dim)] + [1] * (3 - dim)
-    p = [_ptr(t) for t in luts] + [None] * (6 - 2 * dim)
-    _call("lago_fluid_operator", Fmv, _ptr(Fmv), int(bool(inverse)), *p, float(alpha), float(beta), float(gamma), dim,
-          Fmv.size(0), sh[0], sh[1], sh[2])
+    sh = Fmv.shape[2:2 + dim]
+    luts = _check_luts("fluid_operator", Fmv, cosluts, sinluts, sh)
+    _call("lago_fluid_operator", Fmv, _ptr(Fmv), int(bool(inverse)), *_pad([_ptr(t) for t in luts], None, 6), float(alpha),
+          float(beta), float(gamma), dim, Fmv.size(0), *_pad(sh, 1))
     return None
 
 
@@ -1209,26 +1242,17 @@ def fluid_metric(mv, inverse, cosluts, sinluts, alpha, beta, gamma, lut_generati
     `out_scale`: a factor on the result, applied to the finished value (the bits of `result * out_scale`) inside the
     last kernel where that kernel can take it (lago_fluid_metric_scaled)."""
     _check_input(mv, "mv")
-    dim, nx, ny, nz = _spatial(mv)
-    if dim not in (2, 3):
-        raise RuntimeError("Only two- and three-dimensional fluid metric is supported")
+    dim, nx, ny, nz = _spatial_frame(mv, "Only two- and three-dimensional fluid metric is supported")
     if mv.size(1) != dim:
         raise RuntimeError("Vector field has incorrect shape for dimension")
     if len(cosluts) != dim or len(sinluts) != dim:
         raise RuntimeError(f"Must provide same number of LUTs as spatial dimension '{dim}'")
     csh = list(mv.shape[2:])
     csh[-1] = csh[-1] // 2 + 1
-    luts = []
-    for d in range(dim):
-        for t in (cosluts[d], sinluts[d]):
-            if t.dtype != mv.dtype:
-                raise RuntimeError("Type of LUTs must equal that of image")
-            if not t.is_cuda or t.device != mv.device or t.numel() != csh[d]:
-                raise RuntimeError("fluid_metric: LUT on wrong device or of wrong length")
-            luts.append(t.contiguous())
+    luts = _check_luts("fluid_metric", mv, cosluts, sinluts, csh)
     out = torch.empty_like(mv)
     work = torch.empty((mv.size(0), dim, *csh, 2), dtype=mv.dtype, device=mv.device)
-    p = [_ptr(t) for t in luts] + [None] * (6 - 2 * dim)
+    p = _pad([_ptr(t) for t in luts], None, 6)
     if float(out_scale) != 1.0:
         _call("lago_fluid_metric_scaled", mv, _ptr(out), _ptr(mv), _ptr(work), int(lut_generation), int(bool(inverse)), *p,
               float(alpha), float(beta), float(gamma), dim, mv.size(0), nx, ny, nz, float(out_scale))
@@ -1236,6 +1260,9 @@ def fluid_metric(mv, inverse, cosluts, sinluts, alpha, beta, gamma, lut_generati
     _call("lago_fluid_metric", mv, _ptr(out), _ptr(mv), _ptr(work), int(lut_generation), int(bool(inverse)), *p, float(alpha), float(beta),
           float(gamma), dim, mv.size(0), nx, ny, nz)
     return out
+
+
+_AFFINE_DIMS = "Only two- and three-dimensional affine interpolation is supported"
 
 
 def affine_interp_forward(I, A, T):
@@ -1247,15 +1274,11 @@ def affine_interp_forward(I, A, T):
     _same(I, A, T)
     if A.size(0) != T.size(0):
         raise RuntimeError("A and T must have same first dimension")
-    dim, nx, ny, nz = _spatial(I)
-    if dim not in (2, 3):
-        raise RuntimeError("Only two- and three-dimensional affine interpolation is supported")
+    dim, nx, ny, nz = _spatial_frame(I, _AFFINE_DIMS)
     if tuple(A.shape[1:]) != (dim, dim) or tuple(T.shape[1:]) != (dim,):
         raise RuntimeError("affine_interp_forward: A must be (N, d, d) and T (N, d)")
     nn = A.size(0)
-    bc = I.size(0) == 1 and nn > 1
-    if not bc and I.size(0) != nn:
-        raise RuntimeError("affine_interp_forward: batch sizes of I and A are incompatible")
+    bc = _broadcast(I, nn, "affine_interp_forward: batch sizes of I and A are incompatible")
     out = torch.empty((nn, I.size(1)) + tuple(I.shape[2:]), dtype=I.dtype, device=I.device)
     _call("lago_affine_interp_forward", I, _ptr(out), _ptr(I), _ptr(A), _ptr(T), dim, nn, I.size(1), nx, ny, nz, int(bc))
     return out
@@ -1272,13 +1295,12 @@ def affine_interp_backward(grad_out, I, A, T, need_I, need_A, need_T):
         raise RuntimeError("I and grad_out must have same number of channels")
     if A.size(0) != T.size(0):
         raise RuntimeError("A and T must have same first dimension")
-    dim, nx, ny, nz = _spatial(I)
-    if dim not in (2, 3):
-        raise RuntimeError("Only two- and three-dimensional affine interpolation is supported")
+    dim, nx, ny, nz = _spatial_frame(I, _AFFINE_DIMS)
     nn = grad_out.size(0)
-    bc = I.size(0) == 1 and nn > 1
-    if A.size(0) != nn or tuple(grad_out.shape[2:]) != tuple(I.shape[2:]) or (not bc and I.size(0) != nn):
-        raise RuntimeError("affine_interp_backward: grad_out / I / A shapes are inconsistent")
+    inconsistent = "affine_interp_backward: grad_out / I / A shapes are inconsistent"
+    if A.size(0) != nn or tuple(grad_out.shape[2:]) != tuple(I.shape[2:]):
+        raise RuntimeError(inconsistent)
+    bc = _broadcast(I, nn, inconsistent)
     empty = lambda: torch.zeros((0,), dtype=I.dtype, device=I.device)
     d_I = torch.empty_like(I) if need_I else empty()
     d_A = torch.empty_like(A) if need_A else empty()
@@ -1288,33 +1310,19 @@ def affine_interp_backward(grad_out, I, A, T, need_I, need_A, need_T):
     return [d_I, d_A, d_T]
 
 
-def _overlaps(a, b):
-    """Do the byte ranges of two contiguous tensors intersect?  (a partially overlapping view counts: the kernel
-    gathers from its inputs while it writes `out`)"""
-    a0, b0 = a.data_ptr(), b.data_ptr()
-    return a.numel() > 0 and b.numel() > 0 and a0 < b0 + b.numel() * b.element_size() and b0 < a0 + a.numel() * a.element_size()
-
-
 def compose(u, v, ds=1.0, dt=1.0, out=None, near_identity=False):
     """Fused deform.compose (deform.py:53-55): ds*u + dt*interp(v, u, dt=ds) in one kernel.
     Not part of the reference's extension surface; u and v are (N, d, *spatial) vector fields.  `out`: a contiguous
     tensor of their shape to write into (it must not alias u or v).  `near_identity`: a hint that |ds*u| stays below one
     voxel (the Euler step of a shoot); it selects a kernel (`set_compose_near`), never a value."""
-    _check_input(u, "u")
-    _check_input(v, "v")
-    _same(u, v)
-    dim, nx, ny, nz = _spatial(u)
-    if dim not in (2, 3):
-        raise RuntimeError("Only two- and three-dimensional interpolation is supported")
+    _check_inputs((("u", u), ("v", v)))
+    dim, nx, ny, nz = _spatial_frame(u, "Only two- and three-dimensional interpolation is supported")
     if u.shape != v.shape or u.size(1) != dim:
         raise RuntimeError("compose: u and v must be vector fields of the same shape")
     if out is None:
         out = torch.empty_like(u)
     else:
-        _check_input(out, "out")
-        _same(u, out)
-        if out.shape != u.shape or _overlaps(out, u) or _overlaps(out, v):
-            raise RuntimeError("compose: out must have the shape of u and must not alias an input")
+        _check_dest(out, "out", u, "compose: out must have the shape of u and must not alias an input", u, v)
     _call("lago_compose_near" if near_identity else "lago_compose", u, _ptr(out), _ptr(u), _ptr(v), float(ds), float(dt), dim,
           u.size(0), nx, ny, nz)
     return out
@@ -1335,13 +1343,9 @@ def lincomb(terms, out=None):
     if out is None:
         out = torch.empty_like(xs[0])
     else:
-        _check_input(out, "out")
-        _same(xs[0], out)
-        if out.shape != xs[0].shape:
-            raise RuntimeError("lincomb: shapes differ")
-    ptrs = [_ptr(x) for x in xs] + [None] * (4 - len(xs))
-    cs = [float(c) for c, _ in terms] + [0.0] * (4 - len(terms))
-    _call("lago_lincomb", xs[0], _ptr(out), len(terms), *ptrs, *cs, xs[0].numel())
+        _check_dest(out, "out", xs[0], "lincomb: shapes differ")
+    _call("lago_lincomb", xs[0], _ptr(out), len(terms), *_pad([_ptr(x) for x in xs], None, 4),
+          *_pad([float(c) for c, _ in terms], 0.0, 4), xs[0].numel())
     return out
 
 
@@ -1351,27 +1355,11 @@ def interp_backward_fused(grad_out, I, u, dt, need_I, d_u=None, addgo=None, d_I=
     compose's and Ad_star's backward without their extra passes; with `d_I` given the splat is added onto it
     instead of onto zeros.  Returns [d_I, d_u].  Not part of the reference's extension surface
     (include/lagomorph_hip.h: lago_interp_backward_fused)."""
-    _check_input(grad_out, "grad_out")
-    _check_input(I, "I")
-    _check_input(u, "u")
-    _same(I, u, grad_out)
-    dim, nx, ny, nz = _spatial(I)
-    if dim not in (2, 3):
-        raise RuntimeError("Only two- and three-dimensional interpolation is supported")
-    nn = max(u.size(0), I.size(0))
-    bc = I.size(0) < nn
-    if (bc and I.size(0) != 1) or u.size(0) != nn:
-        raise RuntimeError("interp_backward: batch sizes of I and u are incompatible")
-    if (tuple(grad_out.shape) != (nn, I.size(1)) + tuple(I.shape[2:]) or u.dim() != I.dim() or u.size(1) != dim
-            or tuple(u.shape[2:]) != tuple(I.shape[2:])):
-        raise RuntimeError("interp_backward: grad_out / I / u shapes are inconsistent")
+    dim, nx, ny, nz, nn, bc = _interp_backward_args(grad_out, I, u)
     if (d_u is None) == (addgo is None):
         raise RuntimeError("interp_backward_fused: give exactly one of d_u (accumulate) and addgo")
     if d_u is not None:
-        _check_input(d_u, "d_u")
-        _same(u, d_u)
-        if d_u.shape != u.shape:
-            raise RuntimeError("interp_backward_fused: d_u must have the shape of u")
+        _check_dest(d_u, "d_u", u, "interp_backward_fused: d_u must have the shape of u")
         mode, ag = 1, 0.0
     else:
         if I.size(1) != dim:
@@ -1380,9 +1368,8 @@ def interp_backward_fused(grad_out, I, u, dt, need_I, d_u=None, addgo=None, d_I=
         mode, ag = 2, float(addgo)
     imode = 0
     if d_I is not None:
-        _check_input(d_I, "d_I")
-        _same(I, d_I)
-        if d_I.shape != I.shape or not need_I:
+        _check_dest(d_I, "d_I", I, "interp_backward_fused: d_I must have the shape of I (and need_I be set)")
+        if not need_I:
             raise RuntimeError("interp_backward_fused: d_I must have the shape of I (and need_I be set)")
         imode = 1
     else:
@@ -1396,12 +1383,8 @@ def Ad_star(phiinv, m, save_resampled=False):
     """Fused adjrep.Ad_star (adjrep.py:86-97): jacobian_times_vectorfield(phiinv, interp(m, phiinv),
     displacement=True) in one kernel.  Not part of the reference's extension surface.  With save_resampled the
     resampled momentum interp(m, phiinv) is returned as well: (out, mphiinv)."""
-    _check_input(phiinv, "phiinv")
-    _check_input(m, "m")
-    _same(phiinv, m)
-    dim, nx, ny, nz = _spatial(phiinv)
-    if dim not in (2, 3):
-        raise RuntimeError("Only two- and three-dimensional fields are supported")
+    _check_inputs((("phiinv", phiinv), ("m", m)))
+    dim, nx, ny, nz = _spatial_frame(phiinv, "Only two- and three-dimensional fields are supported")
     if phiinv.shape != m.shape or m.size(1) != dim:
         raise RuntimeError("Ad_star: phiinv and m must be vector fields of the same shape")
     out = torch.empty_like(m)
@@ -1413,12 +1396,8 @@ def Ad_star(phiinv, m, save_resampled=False):
 def ad_star(v, m):
     """Fused adjrep.ad_star (adjrep.py:69-83): jacobian_times_vectorfield(v, m, transpose=True) minus
     jacobian_times_vectorfield_adjoint(m, v) in one kernel.  Not part of the reference's extension surface."""
-    _check_input(v, "v")
-    _check_input(m, "m")
-    _same(v, m)
-    dim, nx, ny, nz = _spatial(v)
-    if dim not in (2, 3):
-        raise RuntimeError("Only two- and three-dimensional jacobian times vectorfield is supported")
+    _check_inputs((("v", v), ("m", m)))
+    dim, nx, ny, nz = _spatial_frame(v, _JTV_DIMS)
     if v.shape != m.shape or m.size(1) != dim:
         raise RuntimeError("ad_star: v and m must be vector fields of the same shape")
     out = torch.empty_like(m)
@@ -1426,26 +1405,26 @@ def ad_star(v, m):
     return out
 
 
+_REGRID_DIMS = "Only two- and three-dimensional regridding is supported"
+
+
 def _vec3(x, dim, what):
     x = list(x)
     if len(x) != dim:
         raise RuntimeError(f"{what} should be vector of size d (not 2+d)")
-    return (ctypes.c_double * 3)(*([float(v) for v in x] + [0.0] * (3 - dim)))
+    return (ctypes.c_double * 3)(*_pad([float(v) for v in x], 0.0))
 
 
 def regrid_forward(I, shape, origin, spacing):
     """cuda/affine.cu:683-734"""
     _check_input(I, "I")
-    dim, nx, ny, nz = _spatial(I)
-    if dim not in (2, 3):
-        raise RuntimeError("Only two- and three-dimensional regridding is supported")
+    dim, nx, ny, nz = _spatial_frame(I, _REGRID_DIMS)
     shape = [int(s) for s in shape]
     if len(shape) != dim:
         raise RuntimeError("Shape should be vector of size d (not 2+d)")
     O, S = _vec3(origin, dim, "Origin"), _vec3(spacing, dim, "Spacing")
-    N = shape + [1] * (3 - dim)
     out = torch.empty(tuple(I.shape[:2]) + tuple(shape), dtype=I.dtype, device=I.device)
-    _call("lago_regrid_forward", I, _ptr(out), _ptr(I), dim, I.size(0), I.size(1), nx, ny, nz, N[0], N[1], N[2], O, S)
+    _call("lago_regrid_forward", I, _ptr(out), _ptr(I), dim, I.size(0), I.size(1), nx, ny, nz, *_pad(shape, 1), O, S)
     return out
 
 
@@ -1457,9 +1436,7 @@ REGRID_BACKWARD_SEPARABLE = 1
 def regrid_backward(grad_out, inshape, shape, origin, spacing):
     """cuda/affine.cu:802-855"""
     _check_input(grad_out, "grad_out")
-    dim = grad_out.dim() - 2
-    if dim not in (2, 3):
-        raise RuntimeError("Only two- and three-dimensional regridding is supported")
+    dim = _spatial_frame(grad_out, _REGRID_DIMS)[0]
     inshape = [int(s) for s in inshape]
     shape = [int(s) for s in shape]
     if len(inshape) != dim:
@@ -1467,8 +1444,7 @@ def regrid_backward(grad_out, inshape, shape, origin, spacing):
     if len(shape) != dim or list(grad_out.shape[2:]) != shape:
         raise RuntimeError("Shape should be vector of size d (not 2+d)")
     O, S = _vec3(origin, dim, "Origin"), _vec3(spacing, dim, "Spacing")
-    n3 = inshape + [1] * (3 - dim)
-    N = shape + [1] * (3 - dim)
+    n3, N = _pad(inshape, 1), _pad(shape, 1)
     d_I = torch.empty(tuple(grad_out.shape[:2]) + tuple(inshape), dtype=grad_out.dtype, device=grad_out.device)
     if REGRID_BACKWARD_SEPARABLE and all(S[d] > 0 for d in range(dim)) and d_I.numel() and grad_out.numel():
         # axis by axis in gather form (no atomics, deterministic): two temporaries, each as large as the biggest

@@ -64,9 +64,8 @@ def _check(u, kind, spacing, what, scale=None):
     if scale is not None and not isinstance(scale, torch.Tensor):
         raise TypeError("scale must be a torch.Tensor or None")
     k = _kind(kind)
-    dim = u.dim() - 2
-    if dim not in (2, 3):
-        raise RuntimeError(f"{what}: u must be a field of shape (N, C, *spatial) with two or three spatial axes, got shape {tuple(u.shape)}")
+    dim = _ext._spatial_frame(u, f"{what}: u must be a field of shape (N, C, *spatial) with two or three spatial axes, "
+                                 f"got shape {tuple(u.shape)}")[0]
     sp = _spacing(spacing, dim)
     named = (("u", u),)
     if scale is not None:
@@ -77,10 +76,6 @@ def _check(u, kind, spacing, what, scale=None):
     return k, dim, sp
 
 
-def _extents(u, dim):
-    return tuple(u.shape[2:]) + (1,) * (3 - dim)
-
-
 def _energy(u, kind, spacing):
     """E (N,) by lago_field_energy (csrc/energy.hip: energy_tile_kernel, energy_sum_kernel); the scratch of per-tile
     partial sums is allocated here."""
@@ -88,10 +83,8 @@ def _energy(u, kind, spacing):
     N, C = u.size(0), u.size(1)
     if u.numel() == 0:
         return torch.zeros((N,), dtype=u.dtype, device=u.device)
-    n = _extents(u, dim)
-    elems = int(_ext._lib.lago_field_energy_scratch_elems(k, dim, N, C, *n))
-    if elems < 0:
-        raise RuntimeError(_ext._lib.lago_last_error().decode("utf-8", "replace"))
+    n = _ext._pad(u.shape[2:], 1)
+    elems = _ext._scratch_elems(_ext._lib.lago_field_energy_scratch_elems, k, dim, N, C, *n)
     E = torch.empty((N,), dtype=u.dtype, device=u.device)
     scratch = torch.empty((elems,), dtype=u.dtype, device=u.device)
     _ext._call("lago_field_energy", u, _ext._ptr(E), _ext._ptr(u), _ext._ptr(scratch), elems, k, dim, N, C, *n, (ctypes.c_double * dim)(*sp))
@@ -104,7 +97,7 @@ def _operator(u, kind, spacing, scale):
     out = torch.empty_like(u)
     if u.numel() == 0:
         return out
-    _ext._call("lago_field_energy_operator", u, _ext._ptr(out), _ext._ptr(u), _ext._ptr(scale), k, dim, u.size(0), u.size(1), *_extents(u, dim),
+    _ext._call("lago_field_energy_operator", u, _ext._ptr(out), _ext._ptr(u), _ext._ptr(scale), k, dim, u.size(0), u.size(1), *_ext._pad(u.shape[2:], 1),
                (ctypes.c_double * dim)(*sp))
     return out
 

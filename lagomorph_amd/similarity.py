@@ -12,17 +12,25 @@ from .smooth import _plan
 REDUCTIONS = ("mean", "sum", "none")
 
 
-def _check(I, J, sigma, truncate, mode, eps):
-    """(radii, taps) after the argument checks that need no device."""
-    for x, nm in ((I, "I"), (J, "J")):
-        if not isinstance(x, torch.Tensor):
-            raise TypeError(f"{nm} must be a torch.Tensor")
-    if J.shape != I.shape:
-        raise RuntimeError(f"lncc: I {tuple(I.shape)} and J {tuple(J.shape)} must have the same shape")
+def _pair(I, J, what):
+    """The image pair of the similarity `what`: two tensors of one shape and dtype, wherever they live.  The binding's own
+    pair checks (lagomorph_ext: _check_lncc_pair, _check_mi) go on to the dtype's kind, the axes and the device."""
+    lagomorph_ext._check_tensors((("I", I), ("J", J)))
+    lagomorph_ext._check_same_shape(I, J, what)
     if J.dtype != I.dtype:
-        raise RuntimeError(f"lncc: dtype mismatch ({I.dtype} vs {J.dtype})")
+        raise RuntimeError(f"{what}: dtype mismatch ({I.dtype} vs {J.dtype})")
+
+
+def _lncc_eps(eps):
     if not float(eps) >= 0.0:
         raise ValueError(f"lncc: eps must not be negative (got {eps})")
+    return float(eps)
+
+
+def _check(I, J, sigma, truncate, mode, eps):
+    """(radii, taps) after the argument checks that need no device."""
+    _pair(I, J, "lncc")
+    _lncc_eps(eps)
     return _plan(I, sigma, truncate, mode)
 
 
@@ -98,10 +106,8 @@ class LNCCSimilarity:
 
     def __init__(self, sigma, truncate=4.0, mode="wrap", eps=1e-5):
         self.sigma, self.truncate, self.mode, self.eps = sigma, float(truncate), mode, float(eps)
-        if mode not in lagomorph_ext.GAUSS_MODES:
-            raise ValueError(f"LNCCSimilarity: unknown mode {mode!r} (one of {sorted(lagomorph_ext.GAUSS_MODES)})")
-        if not self.eps >= 0.0:
-            raise ValueError(f"lncc: eps must not be negative (got {eps})")
+        lagomorph_ext._gauss_mode("LNCCSimilarity", mode)
+        _lncc_eps(eps)
 
     def __call__(self, Idef, img):
         return lncc_loss(Idef, img, self.sigma, truncate=self.truncate, mode=self.mode, eps=self.eps, reduction="sum")
@@ -122,13 +128,7 @@ def _auto_range(x, name):
 
 def _mi_check(I, J, bins, range_I, range_J):
     """(bins, range_I, range_J) after the argument checks; a range of None is taken from the tensor."""
-    for x, nm in ((I, "I"), (J, "J")):
-        if not isinstance(x, torch.Tensor):
-            raise TypeError(f"{nm} must be a torch.Tensor")
-    if J.shape != I.shape:
-        raise RuntimeError(f"mutual_information: I {tuple(I.shape)} and J {tuple(J.shape)} must have the same shape")
-    if J.dtype != I.dtype:
-        raise RuntimeError(f"mutual_information: dtype mismatch ({I.dtype} vs {J.dtype})")
+    _pair(I, J, "mutual_information")
     bins = lagomorph_ext.mi_bins(bins)
     range_I = _auto_range(I, "range_I") if range_I is None else lagomorph_ext.mi_range(range_I, "range_I")
     range_J = _auto_range(J, "range_J") if range_J is None else lagomorph_ext.mi_range(range_J, "range_J")

@@ -40,11 +40,8 @@ def _per_axis(sigma, dim):
 
 def _plan(x, sigma, truncate, mode):
     """(radii, taps) per spatial axis after the argument checks that need no device."""
-    if mode not in lagomorph_ext.GAUSS_MODES:
-        raise ValueError(f"gaussian_smooth: unknown mode {mode!r} (one of {sorted(lagomorph_ext.GAUSS_MODES)})")
-    dim = x.dim() - 2
-    if dim not in (2, 3):
-        raise RuntimeError("Only two- and three-dimensional gaussian smoothing is supported")
+    lagomorph_ext._gauss_mode("gaussian_smooth", mode)
+    dim = lagomorph_ext._spatial_frame(x, lagomorph_ext._GAUSS_DIMS)[0]
     sig = _per_axis(sigma, dim)
     radii = [_radius(s, float(truncate)) for s in sig]
     for s, r in zip(sig, radii):
@@ -88,7 +85,6 @@ def gaussian_smooth(x, sigma, truncate=4.0, mode="wrap", alpha=1.0):
 
     Non-contiguous input is made contiguous; the result is always a new tensor.  Deterministic (no atomics), and
     differentiable to any order (the operator is its own adjoint)."""
-    if not isinstance(x, torch.Tensor):
-        raise TypeError("x must be a torch.Tensor")
+    lagomorph_ext._check_tensors((("x", x),))
     _plan(x, sigma, truncate, mode)   # argument errors before autograd records anything
     return GaussianSmoothFunction.apply(x, sigma, float(truncate), mode, float(alpha))
