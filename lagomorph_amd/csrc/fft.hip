@@ -19,40 +19,13 @@
 #include <memory>
 #include <map>
 #include <mutex>
+#include <type_traits>
 #include <vector>
 
-#include "common.hpp"
+#include "fluid.hpp"
 
 namespace lago {
 
-template <typename R>
-int fluid_operator_impl(R *Fm, int inverse, const R *cosX, const R *sinX, const R *cosY, const R *sinY,
-                        const R *cosZ, const R *sinZ, double alpha, double beta, double gamma, int dim,
-                        int64_t nn, int64_t nx, int64_t ny, int64_t nz, void *stream, double scale);  // metric.hip
-
-// fftx.hip
-int fluid_coef_launch(float *tab, int inverse, const float *cosX, const float *sinX, const float *cosY,
-                      const float *sinY, const float *cosZ, const float *sinZ, double alpha, double beta,
-                      double gamma, int64_t nx, int64_t ny, int64_t nzc, int split, hipStream_t s);
-bool fluid_xpass_supported(int64_t nx);
-// fft3.hip
-bool fluid_native_supported(int64_t nx, int64_t ny, int64_t nz);
-int fluid_metric_native(float *out, const float *m, float *work, const float *tab, int inverse, int64_t nn,
-                        int64_t nx, int64_t ny, int64_t nz, double scale, hipStream_t s, float oscale);
-int fluid_xpass_launch(float *F, const float *tab, int inverse, int64_t nn, int64_t nx, int64_t ny, int64_t nzc,
-                       double scale, hipStream_t s);
-bool fluid2d_supported(int64_t h, int64_t w);
-int fluid_metric_2d(float *out, const float *m, int inverse, const float *cosX, const float *sinX, const float *cosY,
-                    const float *sinY, double alpha, double beta, double gamma, int64_t nn, int64_t h, int64_t w,
-                    hipStream_t s, float oscale);
-// fftg.hip
-bool fluid_generic_supported(int dim, int64_t nx, int64_t ny, int64_t nz, size_t esize);
-void bluestein_cache_clear();   // fftg.hip
-int bluestein_cache_entries();
-template <typename R>
-int fluid_metric_generic(R *out, const R *m, R *work, int inverse, const R *cosX, const R *sinX, const R *cosY, const R *sinY,
-                         const R *cosZ, const R *sinZ, double alpha, double beta, double gamma, int dim, int64_t nn, int64_t nx,
-                         int64_t ny, int64_t nz, hipStream_t s);
 // 0: rocFFT 3D plan + operator kernel; 1: rocFFT 2D (y, z) plan + fused x pass (fftx.hip);
 // 2: three LDS-tiled passes, no rocFFT (fft3.hip), falling back to 1 / 0 where the shape is not supported;
 // 3 (default): the same tuned passes, and the GENERIC hand-written passes (fftg.hip) for everything else -- no rocFFT.
@@ -369,9 +342,8 @@ struct SpotCheck {
     }
 };
 
-static int get_coef(CoefRef &ref, int64_t gen, int inverse, const float *cosX, const float *sinX, const float *cosY,
-                    const float *sinY, const float *cosZ, const float *sinZ, double alpha, double beta, double gamma,
-                    int64_t nx, int64_t ny, int64_t nz, int split, hipStream_t s) {
+static int get_coef(CoefRef &ref, int64_t gen, int inverse, const FluidOp<float> &op, int64_t nx, int64_t ny, int64_t nz,
+                    int split, hipStream_t s) {
     int device = 0;
     LAGO_HIP_TRY(hipGetDevice(&device));
     const int64_t nzc = nz / 2 + 1;
@@ -379,14 +351,14 @@ static int get_coef(CoefRef &ref, int64_t gen, int inverse, const float *cosX, c
     std::lock_guard<std::mutex> lk(g_plan_mu);
     for (const CoefRef &t : g_tabs)
         if (t->gen == gen && t->nx == nx && t->ny == ny && t->nz == nz && t->inverse == inverse && t->device == device &&
-            t->split == split && t->a == alpha && t->b == beta && t->g == gamma) {
+            t->split == split && t->a == op.alpha && t->b == op.beta && t->g == op.gamma) {
             ref = t;
             return LAGO_OK;
         }
     CoefRef t = std::make_shared<CoefTab>();
-    *t = CoefTab{gen, nx, ny, nz, inverse, device, split, alpha, beta, gamma, (size_t)nx * ny * nzc * 6 * sizeof(float), nullptr};
+    *t = CoefTab{gen, nx, ny, nz, inverse, device, split, op.alpha, op.beta, op.gamma, (size_t)nx * ny * nzc * 6 * sizeof(float), nullptr};
     LAGO_HIP_TRY(hipMalloc((void **)&t->d, t->bytes));  // on failure below ~CoefTab frees it
-    int rc = fluid_coef_launch(t->d, inverse, cosX, sinX, cosY, sinY, cosZ, sinZ, alpha, beta, gamma, nx, ny, nzc, split, s);
+    int rc = fluid_coef_launch(t->d, inverse, op, nx, ny, nzc, split, s);
     if (rc != LAGO_OK) return rc;
     // one-time: the table is shared by later calls on ANY stream, so it must be complete before it is
     // published (steady-state calls never synchronise)
@@ -435,17 +407,15 @@ static hipfftResult exec_on(hipfftHandle plan, hipStream_t s, F &&exec) {
 
 // float32, 3D, power-of-two nx: rocFFT does the (y, z) transforms as a batched 2D real plan, the
 // x transform + operator + inverse x transform are one kernel (fftx.hip).
-static int fluid_metric_xpass(float *out, const float *m, float *work, int64_t gen, int inverse, const float *cosX,
-                              const float *sinX, const float *cosY, const float *sinY, const float *cosZ,
-                              const float *sinZ, double alpha, double beta, double gamma, int64_t nn, int64_t nx,
-                              int64_t ny, int64_t nz, hipStream_t s) {
+static int fluid_metric_xpass(float *out, const float *m, float *work, int64_t gen, int inverse, const FluidOp<float> &op,
+                              int64_t nn, int64_t nx, int64_t ny, int64_t nz, hipStream_t s) {
     const int n2[3] = {(int)ny, (int)nz, 0};
     FftPlan p;
     int rc = get_plan(p, 2, n2, (int)(nn * 3 * nx), 0);
     if (rc != LAGO_OK) return rc;
     const int64_t nzc = nz / 2 + 1;
     CoefRef tab;
-    rc = get_coef(tab, gen, inverse, cosX, sinX, cosY, sinY, cosZ, sinZ, alpha, beta, gamma, nx, ny, nz, 0, s);
+    rc = get_coef(tab, gen, inverse, op, nx, ny, nz, 0, s);
     if (rc != LAGO_OK) return rc;
     hipfftResult r = exec_on(p.fwd, s, [&] { return hipfftExecR2C(p.fwd, (hipfftReal *)m, (hipfftComplex *)work); });
     if (r != HIPFFT_SUCCESS) return fail_fft(r, "hipfftExecR2C(2D)");
@@ -470,34 +440,29 @@ __global__ __launch_bounds__(256) void scale_inplace_kernel(R *__restrict__ x, s
 }
 
 template <typename R>
-static int fluid_metric_unscaled(R *out, const R *m, R *work, int64_t gen, int inverse, const R *cosX, const R *sinX,
-                                 const R *cosY, const R *sinY, const R *cosZ, const R *sinZ, double alpha, double beta,
-                                 double gamma, int dim, int64_t nn, int64_t nx, int64_t ny, int64_t nz, void *stream,
-                                 R oscale, bool &scaled);
+static int fluid_metric_unscaled(R *out, const R *m, R *work, int64_t gen, int inverse, const FluidOp<R> &op, int dim,
+                                 int64_t nn, int64_t nx, int64_t ny, int64_t nz, hipStream_t s, R oscale, bool &scaled);
 
 // out = oscale * irfftn(operator(rfftn(m))): the factor multiplies the finished value (the bits of `out * oscale` in the
 // field's precision) -- inside the last kernel of the tuned 3D passes and of the fused 2D kernel, as one more pass on
 // the other paths
 template <typename R>
-static int fluid_metric_impl(R *out, const R *m, R *work, int64_t gen, int inverse, const R *cosX, const R *sinX, const R *cosY,
-                             const R *sinY, const R *cosZ, const R *sinZ, double alpha, double beta, double gamma,
-                             int dim, int64_t nn, int64_t nx, int64_t ny, int64_t nz, void *stream, double out_scale) {
+static int fluid_metric_impl(R *out, const R *m, R *work, int64_t gen, int inverse, const FluidOp<R> &op, int dim, int64_t nn,
+                             int64_t nx, int64_t ny, int64_t nz, hipStream_t s, double out_scale) {
     const R f = (R)out_scale;
     bool scaled = false;
-    int rc = fluid_metric_unscaled<R>(out, m, work, gen, inverse, cosX, sinX, cosY, sinY, cosZ, sinZ, alpha, beta, gamma, dim,
-                                      nn, nx, ny, nz, stream, f, scaled);
+    int rc = fluid_metric_unscaled<R>(out, m, work, gen, inverse, op, dim, nn, nx, ny, nz, s, f, scaled);
     if (rc != LAGO_OK || scaled || f == (R)1 || nn == 0) return rc;
     const size_t n = (size_t)nn * dim * nx * ny * (dim == 2 ? 1 : nz);
     const unsigned grid = (unsigned)std::min<size_t>((n + 255) / 256, 256 * 16);
-    hipLaunchKernelGGL(scale_inplace_kernel<R>, dim3(grid), dim3(256), 0, (hipStream_t)stream, out, n, f);
-    return finish_launch((hipStream_t)stream, "fluid_metric (scale)");
+    hipLaunchKernelGGL(scale_inplace_kernel<R>, dim3(grid), dim3(256), 0, s, out, n, f);
+    return finish_launch(s, "fluid_metric (scale)");
 }
 
 template <typename R>
-static int fluid_metric_unscaled(R *out, const R *m, R *work, int64_t gen, int inverse, const R *cosX, const R *sinX,
-                                 const R *cosY, const R *sinY, const R *cosZ, const R *sinZ, double alpha, double beta,
-                                 double gamma, int dim, int64_t nn, int64_t nx, int64_t ny, int64_t nz, void *stream,
-                                 R oscale, bool &scaled) {
+static int fluid_metric_unscaled(R *out, const R *m, R *work, int64_t gen, int inverse, const FluidOp<R> &op, int dim,
+                                 int64_t nn, int64_t nx, int64_t ny, int64_t nz, hipStream_t s, R oscale, bool &scaled) {
+    constexpr bool kF32 = std::is_same<R, float>::value;   // the tuned paths are float32 only
     if (dim != 2 && dim != 3) return fail_invalid("Only two- and three-dimensional fluid metric is supported");
     if (dim == 2) nz = 1;
     if (nn < 0 || nx < 1 || ny < 1 || nz < 1 || nn * dim >= (1ll << 31) || nx * ny * nz >= (1ll << 29))
@@ -505,42 +470,34 @@ static int fluid_metric_unscaled(R *out, const R *m, R *work, int64_t gen, int i
     if (nn == 0) return LAGO_OK;
     if (!out || !m || !work) return fail_invalid("fluid_metric: null pointer");
     // 2D float32 fields whose two component planes fit the LDS together: one kernel for the whole operator (fft3.hip)
-    if (sizeof(R) == 4 && dim == 2 && g_fluid_xpass >= 2 && fluid2d_supported(nx, ny) && nn < (1ll << 31) &&
-        (((uintptr_t)out | (uintptr_t)m) & 15) == 0) {
+    if constexpr (kF32) if (dim == 2 && g_fluid_xpass >= 2 && fluid2d_supported(nx, ny) && nn < (1ll << 31) &&
+                            (((uintptr_t)out | (uintptr_t)m) & 15) == 0) {
         note_path(LP_FLUID_2D);
         scaled = true;
-        return fluid_metric_2d((float *)out, (const float *)m, inverse, (const float *)cosX, (const float *)sinX,
-                               (const float *)cosY, (const float *)sinY, alpha, beta, gamma, nn, nx, ny, (hipStream_t)stream,
-                               (float)oscale);
+        return fluid_metric_2d(out, m, inverse, op, nn, nx, ny, s, oscale);
     }
     // the table-based fast paths need a LUT generation to key their cached coefficient table on
-    if (gen != 0 && sizeof(R) == 4 && dim == 3 && g_fluid_xpass >= 2 && fluid_native_supported(nx, ny, nz) &&
-        (((uintptr_t)out | (uintptr_t)m | (uintptr_t)work) & 15) == 0) {  // 16-byte vector accesses
+    if constexpr (kF32) if (gen != 0 && dim == 3 && g_fluid_xpass >= 2 && fluid_native_supported(nx, ny, nz) &&
+                            (((uintptr_t)out | (uintptr_t)m | (uintptr_t)work) & 15) == 0) {  // 16-byte vector accesses
         CoefRef tab;
-        int rc = get_coef(tab, gen, inverse, (const float *)cosX, (const float *)sinX, (const float *)cosY,
-                          (const float *)sinY, (const float *)cosZ, (const float *)sinZ, alpha, beta, gamma, nx, ny,
-                          nz, 1, (hipStream_t)stream);
+        int rc = get_coef(tab, gen, inverse, op, nx, ny, nz, 1, s);
         if (rc != LAGO_OK) return rc;
         note_path(LP_FLUID_LDS);
         scaled = true;
-        return fluid_metric_native((float *)out, (const float *)m, (float *)work, tab->d, inverse, nn, nx, ny, nz,
-                                   1.0 / ((double)nx * (double)ny * (double)nz), (hipStream_t)stream, (float)oscale);
+        return fluid_metric_native(out, m, work, tab->d, inverse, nn, nx, ny, nz, 1.0 / ((double)nx * (double)ny * (double)nz),
+                                   s, oscale);
     }
     if (g_fluid_xpass >= 3 && fluid_generic_supported(dim, nx, ny, nz, sizeof(R))) {
         note_path(LP_FLUID_GENERIC);
-        return fluid_metric_generic<R>(out, m, work, inverse, cosX, sinX, cosY, sinY, cosZ, sinZ, alpha, beta, gamma, dim, nn,
-                                       nx, ny, nz, (hipStream_t)stream);
+        return fluid_metric_generic<R>(out, m, work, inverse, op, dim, nn, nx, ny, nz, s);
     }
-    if (gen != 0 && sizeof(R) == 4 && dim == 3 && g_fluid_xpass && fluid_xpass_supported(nx) && nn * 3 * nx < (1ll << 31)) {
+    if constexpr (kF32) if (gen != 0 && dim == 3 && g_fluid_xpass && fluid_xpass_supported(nx) && nn * 3 * nx < (1ll << 31)) {
         note_path(LP_FLUID_XPASS);
-        return fluid_metric_xpass((float *)out, (const float *)m, (float *)work, gen, inverse, (const float *)cosX,
-                                  (const float *)sinX, (const float *)cosY, (const float *)sinY, (const float *)cosZ,
-                                  (const float *)sinZ, alpha, beta, gamma, nn, nx, ny, nz, (hipStream_t)stream);
+        return fluid_metric_xpass(out, m, work, gen, inverse, op, nn, nx, ny, nz, s);
     }
     note_path(LP_FLUID_ROCFFT);
     const int n[3] = {(int)nx, (int)ny, (int)nz};
     FftPlan p;
-    hipStream_t s = (hipStream_t)stream;
     int rc = get_plan(p, dim, n, (int)(nn * dim), sizeof(R) == 8);
     if (rc != LAGO_OK) return rc;
     hipfftResult r = exec_on(p.fwd, s, [&] {
@@ -554,8 +511,7 @@ static int fluid_metric_unscaled(R *out, const R *m, R *work, int64_t gen, int i
     // half-spectrum extents: the last axis keeps n/2 + 1 bins
     const int64_t cx = nx, cy = dim == 2 ? ny / 2 + 1 : ny, cz = dim == 3 ? nz / 2 + 1 : 1;
     const double scale = 1.0 / ((double)nx * (double)ny * (double)nz);
-    rc = fluid_operator_impl<R>(work, inverse, cosX, sinX, cosY, sinY, cosZ, sinZ, alpha, beta, gamma, dim, nn, cx, cy,
-                                cz, stream, scale);
+    rc = fluid_operator_impl<R>(work, inverse, op, dim, nn, cx, cy, cz, s, scale);
     if (rc != LAGO_OK) return rc;
     rc = spot.inverse_prepare(work);
     if (rc != LAGO_OK) return rc;
@@ -572,7 +528,6 @@ static int fluid_metric_unscaled(R *out, const R *m, R *work, int64_t gen, int i
 }  // namespace lago
 
 namespace lago {
-void tune_generic_fuse(int on);   // fftg.hip
 // mode 4: as 3 (the default), but the generic passes run the x transforms and the operator as three launches instead of the
 // fused fft_xop_kernel -- the A/B and bit-comparison switch of that fusion
 void tune_fluid(int mode) {
@@ -605,16 +560,18 @@ int lago_fft_plan_state(int *plans, int *verified) {
                                const REAL *cosX, const REAL *sinX, const REAL *cosY, const REAL *sinY,            \
                                const REAL *cosZ, const REAL *sinZ, double alpha, double beta, double gamma,       \
                                int dim, int64_t nn, int64_t nx, int64_t ny, int64_t nz, void *stream) {           \
-        return lago::fluid_metric_impl<REAL>(out, m, work, lut_generation, inverse, cosX, sinX, cosY, sinY, cosZ, \
-                                             sinZ, alpha, beta, gamma, dim, nn, nx, ny, nz, stream, 1.0);         \
+        const lago::FluidOp<REAL> op{cosX, sinX, cosY, sinY, cosZ, sinZ, alpha, beta, gamma};                     \
+        return lago::fluid_metric_impl<REAL>(out, m, work, lut_generation, inverse, op, dim, nn, nx, ny, nz,      \
+                                             (hipStream_t)stream, 1.0);                                           \
     }                                                                                                              \
     int lago_fluid_metric_scaled##SUF(REAL *out, const REAL *m, REAL *work, int64_t lut_generation, int inverse,  \
                                       const REAL *cosX, const REAL *sinX, const REAL *cosY, const REAL *sinY,     \
                                       const REAL *cosZ, const REAL *sinZ, double alpha, double beta,              \
                                       double gamma, int dim, int64_t nn, int64_t nx, int64_t ny, int64_t nz,      \
                                       double out_scale, void *stream) {                                           \
-        return lago::fluid_metric_impl<REAL>(out, m, work, lut_generation, inverse, cosX, sinX, cosY, sinY, cosZ, \
-                                             sinZ, alpha, beta, gamma, dim, nn, nx, ny, nz, stream, out_scale);   \
+        const lago::FluidOp<REAL> op{cosX, sinX, cosY, sinY, cosZ, sinZ, alpha, beta, gamma};                     \
+        return lago::fluid_metric_impl<REAL>(out, m, work, lut_generation, inverse, op, dim, nn, nx, ny, nz,      \
+                                             (hipStream_t)stream, out_scale);                                     \
     }
 LAGO_DEFINE(float, _f32)
 LAGO_DEFINE(double, _f64)

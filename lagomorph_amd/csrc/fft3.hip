@@ -12,6 +12,7 @@
 // spectrum, write out) + the coefficient table, against 14 for rocFFT's 3D plan + operator.
 #include <algorithm>
 #include "fft3_sizes.hpp"
+#include "fluid.hpp"
 
 namespace lago {
 
@@ -129,21 +130,12 @@ __global__ __launch_bounds__((ZYK<NY, NZ>::THREADS)) void zy_inverse_persist_ker
 // ---- 2D fields: the whole FluidMetricOperator.forward (metric.py:11-19) of one batch item in ONE kernel ----------
 // Both component planes of an (H, W) field fit the LDS together up to about 128 x 128 (2 x 66.5 KB): real 2D
 // transform of both (the zy phases above, H along "y", W along "z"), the reference's 2 x 2 operator per frequency
-// (fluid_kernel_2d, cuda/metric.cu:162-218: the expressions and roundings of metric.hip, coefficients straight from
-// the cos / sin LUTs), inverse transform, store: 8 bytes of HBM traffic per value instead of the 28 of
+// (fluid_kernel_2d, cuda/metric.cu:162-218: a FluidBin2 of fluid.hpp, coefficients straight from the cos / sin LUTs of
+// X and Y), inverse transform, store: 8 bytes of HBM traffic per value instead of the 28 of
 // rocFFT R2C + operator kernel + rocFFT C2R (and three launches less).
-template <typename R>
-__device__ __forceinline__ R fl2d_safe_sqrt(R x) {  // cuda/metric.cu:14-18
-    if ((double)x < 1e-8) return (R)1e-4;
-    return (R)sqrtf((float)x);
-}
-
 template <int NY, int NZ, bool INV>
 __global__ __launch_bounds__((ZYK2D<NY, NZ>::THREADS)) void fluid2d_kernel(float *__restrict__ out, const float *__restrict__ m,
-                                                                       const float *__restrict__ cosX, const float *__restrict__ sinX,
-                                                                       const float *__restrict__ cosY, const float *__restrict__ sinY,
-                                                                       double alpha, double beta, double gamma, float scale,
-                                                                       float oscale) {
+                                                                       FluidOp<float> o, float scale, float oscale) {
     using K = ZYK2D<NY, NZ>;
     using SY = typename SzOf<NY>::T;
     using SZH = typename SzOf<NZ / 2>::T;
@@ -164,40 +156,13 @@ __global__ __launch_bounds__((ZYK2D<NY, NZ>::THREADS)) void fluid2d_kernel(float
     for (int w = threadIdx.x; w < NY * (NZH + 1); w += NT) {
         const int kx = w / (NZH + 1), ky = w - kx * (NZH + 1);
         const int at = fl::pos_of<SY>(kx) * PZ + (ky == NZH ? NZH : fl::pos_of<SZH>(ky));
-        const float wx = cosX[kx], wy = cosY[ky];
-        const float lambda = (float)__builtin_fma(alpha, (double)(wx + wy), gamma);
-        const float l00 = (float)__builtin_fma(-beta, (double)wx, (double)lambda);
-        const float l11 = (float)__builtin_fma(-beta, (double)wy, (double)lambda);
-        const float l10 = (float)(beta * (double)sinX[kx] * (double)sinY[ky]);
-        const float L00 = lg_fma(l00, l00, l10 * l10);
-        const float L10 = lg_fma(l00, l10, l10 * l11);
-        const float L11 = lg_fma(l11, l11, l10 * l10);
-        float ooG00 = 0, G10 = 0, ooG11 = 0;
-        if (INV) {  // cuda/metric.cu:20-45
-            ooG00 = (float)(1. / (double)fl2d_safe_sqrt(L00));
-            G10 = L10 * ooG00;
-            ooG11 = lg_fma(-G10, G10, L11);
-            ooG11 = (float)(1. / (double)fl2d_safe_sqrt(ooG11));
-        }
+        FluidBin2<float, INV> op;
+        op.setup(o, kx, ky);
         const float2 a = P0[at], b = P1[at];
-        float X[2] = {a.x, a.y}, Y[2] = {b.x, b.y};
-#pragma unroll
-        for (int q = 0; q < 2; ++q) {
-            float bX = X[q], bY = Y[q];
-            if (INV) {  // cuda/metric.cu:80-101
-                const float y0 = bX * ooG00;
-                const float y1 = lg_fma(-G10, y0, bY) * ooG11;
-                bY = y1 * ooG11;
-                bX = lg_fma(-G10, bY, y0) * ooG00;
-            } else {  // cuda/metric.cu:132-143
-                const float x = lg_fma(L00, bX, L10 * bY);
-                bY = lg_fma(L10, bX, L11 * bY);
-                bX = x;
-            }
-            X[q] = bX * scale; Y[q] = bY * scale;
-        }
-        P0[at] = make_float2(X[0], X[1]);
-        P1[at] = make_float2(Y[0], Y[1]);
+        Cplx<float> X{a.x, a.y}, Y{b.x, b.y};
+        op.apply(X, Y, scale);
+        P0[at] = make_float2(X.re, X.im);
+        P1[at] = make_float2(Y.re, Y.im);
     }
     __syncthreads();
     // what inv_fill does to column 0: FA + i FB (FB = the Nyquist column), so that the inverse y transform returns
@@ -231,25 +196,23 @@ bool fluid2d_supported(int64_t h, int64_t w) {
 }
 
 template <int NY, int NZ>
-static hipError_t fluid2d_launch(float *out, const float *m, int inverse, const float *cosX, const float *sinX,
-                                 const float *cosY, const float *sinY, double alpha, double beta, double gamma,
-                                 int64_t nn, hipStream_t s, float oscale) {
+static hipError_t fluid2d_launch(float *out, const float *m, int inverse, const FluidOp<float> &op, int64_t nn, hipStream_t s,
+                                 float oscale) {
     using K = ZYK2D<NY, NZ>;
     constexpr size_t smem = (size_t)(2 * NY * K::PZ + K::TWN) * sizeof(float2);
     static_assert(smem <= 160 * 1024, "two planes do not fit the LDS");
     const float scale = (float)(1.0 / ((double)NY * (double)NZ));
     return with_flags([&](auto INV) {
-        return launch(fluid2d_kernel<NY, NZ, INV()>, dim3((uint32_t)nn), dim3(K::THREADS), smem, s, out, m, cosX, sinX, cosY,
-                      sinY, alpha, beta, gamma, scale, oscale);
+        return launch(fluid2d_kernel<NY, NZ, INV()>, dim3((uint32_t)nn), dim3(K::THREADS), smem, s, out, m, op, scale,
+                      oscale);
     }, inverse != 0);
 }
 
-int fluid_metric_2d(float *out, const float *m, int inverse, const float *cosX, const float *sinX, const float *cosY,
-                    const float *sinY, double alpha, double beta, double gamma, int64_t nn, int64_t h, int64_t w,
+int fluid_metric_2d(float *out, const float *m, int inverse, const FluidOp<float> &op, int64_t nn, int64_t h, int64_t w,
                     hipStream_t s, float oscale) {
     hipError_t e = hipErrorInvalidValue;
 #define X(H, W) \
-    if (h == H && w == W) e = fluid2d_launch<H, W>(out, m, inverse, cosX, sinX, cosY, sinY, alpha, beta, gamma, nn, s, oscale);
+    if (h == H && w == W) e = fluid2d_launch<H, W>(out, m, inverse, op, nn, s, oscale);
     LAGO_2D_SHAPES(X)
 #undef X
     if (e != hipSuccess) return fail_hip(e, "fluid_metric (2D)");

@@ -458,8 +458,9 @@ LAGO_HD void run_stage(int g, float2 *buf, const float2 *tw, int tid) {
 // ---------------------------------------------------------------------------------------------
 // The per-frequency operator on one frequency bin (three complex components), coefficients as
 // tabulated by fluid_coef_kernel: cuda/metric.cu:103-130 (sharp: Cholesky solve with
-// ooG00 G10 ooG11 G20 G21 ooG22) and :145-160 (flat: L00 L10 L11 L20 L21 L22).  Same expressions
-// and roundings as fluid_kernel in metric.hip.
+// ooG00 G10 ooG11 G20 G21 ooG22) and :145-160 (flat: L00 L10 L11 L20 L21 L22), both parts of each
+// component, then times `scale`: FluidBin3::apply (fluid.hpp) on a table entry.  Also the x pass of
+// fftx.hip; it lives here because this header compiles for the host as well.
 template <bool INV>
 LAGO_HD void fluid_bin(const float *c, float2 &X, float2 &Y, float2 &Z, float scale) {
     const float c0 = c[0], c1 = c[1], c2 = c[2], c3 = c[3], c4 = c[4], c5 = c[5];

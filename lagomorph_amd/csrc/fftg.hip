@@ -30,45 +30,35 @@
 #include <mutex>
 #include <vector>
 
-#include "common.hpp"
-#include "fluid_bin.hpp"
+#include "fluid.hpp"
 
 namespace lago {
 
 template <typename R>
-int fluid_operator_impl(R *Fm, int inverse, const R *cosX, const R *sinX, const R *cosY, const R *sinY,
-                        const R *cosZ, const R *sinZ, double alpha, double beta, double gamma, int dim,
-                        int64_t nn, int64_t nx, int64_t ny, int64_t nz, void *stream, double scale);  // metric.hip
-
-template <typename R>
-struct alignas(2 * sizeof(R)) GC {
-    R re, im;
-};
-template <typename R>
-__device__ __forceinline__ GC<R> cmul(GC<R> a, GC<R> b) {
+__device__ __forceinline__ Cplx<R> cmul(Cplx<R> a, Cplx<R> b) {
     return {a.re * b.re - a.im * b.im, a.re * b.im + a.im * b.re};
 }
 
 template <typename R>
-__device__ __forceinline__ GC<R> cadd(GC<R> a, GC<R> b) { return {a.re + b.re, a.im + b.im}; }
+__device__ __forceinline__ Cplx<R> cadd(Cplx<R> a, Cplx<R> b) { return {a.re + b.re, a.im + b.im}; }
 template <typename R>
-__device__ __forceinline__ GC<R> csub(GC<R> a, GC<R> b) { return {a.re - b.re, a.im - b.im}; }
+__device__ __forceinline__ Cplx<R> csub(Cplx<R> a, Cplx<R> b) { return {a.re - b.re, a.im - b.im}; }
 // a * (sign i)
 template <typename R>
-__device__ __forceinline__ GC<R> cmuli(GC<R> a, int sign) {
-    return sign > 0 ? GC<R>{-a.im, a.re} : GC<R>{a.im, -a.re};
+__device__ __forceinline__ Cplx<R> cmuli(Cplx<R> a, int sign) {
+    return sign > 0 ? Cplx<R>{-a.im, a.re} : Cplx<R>{a.im, -a.re};
 }
 
 template <typename R>
-__device__ __forceinline__ GC<R> root(int k, int n, int sign);   // exp(sign 2 pi i k / n)
+__device__ __forceinline__ Cplx<R> root(int k, int n, int sign);   // exp(sign 2 pi i k / n)
 template <>
-__device__ __forceinline__ GC<double> root<double>(int k, int n, int sign) {
+__device__ __forceinline__ Cplx<double> root<double>(int k, int n, int sign) {
     double sn, cs;
     sincospi(2.0 * (double)k / (double)n, &sn, &cs);
     return {cs, (double)sign * sn};
 }
 template <>
-__device__ __forceinline__ GC<float> root<float>(int k, int n, int sign) {
+__device__ __forceinline__ Cplx<float> root<float>(int k, int n, int sign) {
     double sn, cs;   // in double, rounded once (fft_lds.hpp twiddle(): sincospif of the rounded argument is off by up to six ulps)
     sincospi(2.0 * (double)k / (double)n, &sn, &cs);
     return {(float)cs, (float)sign * (float)sn};
@@ -103,8 +93,8 @@ __device__ __forceinline__ size_t gline_base(const GLines &a, uint32_t l, int n_
 
 // radix-2 / 4 / 8 butterflies on registers: o[u] = sum_t v[t] w^(t u), w = exp(sgn 2 pi i / RR)
 template <typename R, int RR>
-__device__ __forceinline__ void bfly_pow2(const GC<R> (&v)[RR], GC<R> (&o)[RR], int sgn) {
-    typedef GC<R> C;
+__device__ __forceinline__ void bfly_pow2(const Cplx<R> (&v)[RR], Cplx<R> (&o)[RR], int sgn) {
+    typedef Cplx<R> C;
     if constexpr (RR == 2) {
         o[0] = cadd(v[0], v[1]);
         o[1] = csub(v[0], v[1]);
@@ -141,10 +131,10 @@ __device__ __forceinline__ void bfly_pow2(const GC<R> (&v)[RR], GC<R> (&o)[RR], 
 // broadcast.
 // `pre` (Bluestein's second transform, first stage): input point i is taken as conj(x[i] pre[i]).
 template <typename R, int RR>
-__device__ __forceinline__ void stage_fixed(const GC<R> *__restrict__ x, GC<R> *__restrict__ y, const GC<R> *__restrict__ W,
+__device__ __forceinline__ void stage_fixed(const Cplx<R> *__restrict__ x, Cplx<R> *__restrict__ y, const Cplx<R> *__restrict__ W,
                                             const GLines &a, int N, int sgn, int nl, int s, int m, FastDiv ds,
-                                            const GC<R> *__restrict__ pre = nullptr) {
-    typedef GC<R> C;
+                                            const Cplx<R> *__restrict__ pre = nullptr) {
+    typedef Cplx<R> C;
     const int Lp = a.Lp, L = a.L;
     C wr[RR];
     if (RR != 2 && RR != 4 && RR != 8) {
@@ -202,9 +192,9 @@ __device__ __forceinline__ void stage_fixed(const GC<R> *__restrict__ x, GC<R> *
 // multiply-adds per input: with x = a + i b and w = c + i s,  X[u] = (P - Q) + i (R + T),  X[r - u] = (P + Q) + i (T - R),
 // P = sum a c, Q = sum b s, R = sum a s, T = sum b c.  u = 0 (the plain sum) is an item of its own.
 template <typename R>
-__device__ __forceinline__ void stage_any(const GC<R> *__restrict__ x, GC<R> *__restrict__ y, const GC<R> *__restrict__ W,
+__device__ __forceinline__ void stage_any(const Cplx<R> *__restrict__ x, Cplx<R> *__restrict__ y, const Cplx<R> *__restrict__ W,
                                           const GLines &a, int N, int nl, int r, int s, int m, FastDiv ds, FastDiv dr) {
-    typedef GC<R> C;
+    typedef Cplx<R> C;
     const int Lp = a.Lp, L = a.L, wstep = N / r, h = (r + 1) / 2;   // h items per butterfly: u = 0 and (r - 1) / 2 pairs
     const FastDiv dh = dr;
     const int items = m * s * h * L;   // butterflies (m s) x items x lines
@@ -247,9 +237,9 @@ __device__ __forceinline__ void stage_any(const GC<R> *__restrict__ x, GC<R> *__
 // float32: 64 KB instead of 128: two workgroups per CU, or twice the adjacent lines).  The host keeps
 // (N / RR) L <= 256 * (32 / RR), i.e. L N <= 8192.
 template <typename R, int RR>
-__device__ __forceinline__ void stage_inplace(GC<R> *__restrict__ x, const GC<R> *__restrict__ W, const GLines &a, int N, int sgn,
-                                              int nl, int s, int m, FastDiv ds, const GC<R> *__restrict__ pre) {
-    typedef GC<R> C;
+__device__ __forceinline__ void stage_inplace(Cplx<R> *__restrict__ x, const Cplx<R> *__restrict__ W, const GLines &a, int N, int sgn,
+                                              int nl, int s, int m, FastDiv ds, const Cplx<R> *__restrict__ pre) {
+    typedef Cplx<R> C;
     constexpr int TM = 32 / RR;
     const int Lp = a.Lp, L = a.L, nb = (N / RR) * L;
     C v[TM][RR];
@@ -296,14 +286,14 @@ __device__ __forceinline__ void stage_inplace(GC<R> *__restrict__ x, const GC<R>
 // RMAX = 4: the factors are 4 and 2 only (power-of-two lengths, every Bluestein line) -- the kernel then carries neither
 // the odd-radix butterflies nor the direct stage and needs about half the registers: more workgroups per CU.
 template <typename R, int RMAX, bool INPL = false>
-__device__ __forceinline__ GC<R> *run_stages(GC<R> *x, GC<R> *y, const GC<R> *W, const GLines &a, int NP, int sgn, int nl,
-                                             const GC<R> *pre = nullptr) {
+__device__ __forceinline__ Cplx<R> *run_stages(Cplx<R> *x, Cplx<R> *y, const Cplx<R> *W, const GLines &a, int NP, int sgn, int nl,
+                                             const Cplx<R> *pre = nullptr) {
     int n = NP, s = 1;
     for (int f = 0; f < a.nfac; ++f) {
         const int r = a.fac[f], m = n / r;
         __syncthreads();
         if constexpr (RMAX <= 4) {   // (power-of-two lengths: radix 8, 4, 2)
-            const GC<R> *pf = f == 0 ? pre : nullptr;
+            const Cplx<R> *pf = f == 0 ? pre : nullptr;
             if constexpr (INPL) {   // (y == x)
                 if (r == 8) stage_inplace<R, 8>(x, W, a, NP, sgn, nl, s, m, a.ds[f], pf);
                 else if (r == 4) stage_inplace<R, 4>(x, W, a, NP, sgn, nl, s, m, a.ds[f], pf);
@@ -330,7 +320,7 @@ __device__ __forceinline__ GC<R> *run_stages(GC<R> *x, GC<R> *y, const GC<R> *W,
                 default: stage_any<R>(x, y, W, a, NP, nl, r, s, m, a.ds[f], a.dr[f]); break;
             }
         }
-        GC<R> *tmp = x; x = y; y = tmp;
+        Cplx<R> *tmp = x; x = y; y = tmp;
         n = m;
         s *= r;
     }
@@ -341,7 +331,7 @@ __device__ __forceinline__ GC<R> *run_stages(GC<R> *x, GC<R> *y, const GC<R> *W,
 // exp(sign pi i n^2 / N): the chirp of Bluestein's identity n k = (n^2 + k^2 - (k - n)^2) / 2, the argument reduced
 // exactly (n^2 mod 2 N in integers)
 template <typename R>
-__device__ __forceinline__ GC<R> chirp(int n, int N, int sign) {
+__device__ __forceinline__ Cplx<R> chirp(int n, int N, int sign) {
     const unsigned long long q = ((unsigned long long)n * (unsigned long long)n) % (2ull * (unsigned long long)N);
     if constexpr (sizeof(R) == 8) {
         double sn, cs;
@@ -357,9 +347,9 @@ __device__ __forceinline__ GC<R> chirp(int n, int N, int sign) {
 // bhat[k] = FFT_M(d)[k] / M with d[m] = conj(chirp)(|m|) for |m| < N (indices mod M), 0 elsewhere: one workgroup, once
 // per (N, sign, precision) -- lines_pass caches the table
 template <typename R>
-__global__ __launch_bounds__(kBlock) void bluestein_table_kernel(GC<R> *__restrict__ bhat, GLines a) {
+__global__ __launch_bounds__(kBlock) void bluestein_table_kernel(Cplx<R> *__restrict__ bhat, GLines a) {
     extern __shared__ __align__(16) unsigned char lago_fg[];
-    typedef GC<R> C;
+    typedef Cplx<R> C;
     const int N = a.N, M = a.M;
     C *x = reinterpret_cast<C *>(lago_fg), *y = x + M, *W = y + M;   // (a.L = a.Lp = 1)
     for (int k = threadIdx.x; k < M; k += kBlock) {
@@ -375,10 +365,10 @@ __global__ __launch_bounds__(kBlock) void bluestein_table_kernel(GC<R> *__restri
 }
 
 template <typename R, int RMAX, bool INPL = false>
-__global__ __launch_bounds__(kBlock) void fft_lines_kernel(GC<R> *__restrict__ spec, const R *__restrict__ rin, R *__restrict__ rout,
+__global__ __launch_bounds__(kBlock) void fft_lines_kernel(Cplx<R> *__restrict__ spec, const R *__restrict__ rin, R *__restrict__ rout,
                                                            GLines a) {
     extern __shared__ __align__(16) unsigned char lago_fg[];
-    typedef GC<R> C;
+    typedef Cplx<R> C;
     const int N = a.N, L = a.L, Lp = a.Lp;
     const int NB = a.M ? a.M : N;   // rows of the two line buffers and entries of the root table
     C *x = reinterpret_cast<C *>(lago_fg), *y = INPL ? x : x + (size_t)Lp * NB, *W = y + (size_t)Lp * NB;
@@ -484,12 +474,13 @@ __global__ __launch_bounds__(kBlock) void fft_lines_kernel(GC<R> *__restrict__ s
 // each (x forward, operator kernel, x inverse): 5 instead of 7 passes per fluid_metric call on the generic path.  A
 // workgroup takes L adjacent (y, z-bin) columns of one batch item, all three components: 3 L lines in LDS, line index
 // 3 j + c (a column's components adjacent, so the valid lines of a ragged last chunk are contiguous).  The stages are
-// those of fft_lines_kernel (run_stages on the same roots), the operator is fluid_bin.hpp's: the bits of the three
+// those of fft_lines_kernel (run_stages on the same roots), the operator is fluid.hpp's: the bits of the three
 // separate launches.  Lengths that run as Bluestein convolutions keep the separate passes (host); power-of-two lines of 256
 // points and more run their stages in place (INPL: one line buffer, twice the adjacent columns in the same LDS).
+template <typename R>
 struct XopArgs {
-    const void *cosX, *sinX, *cosY, *sinY, *cosZ, *sinZ;
-    double alpha, beta, gamma, scale;
+    FluidOp<R> op;
+    double scale;
     uint32_t cols;      // columns per component plane: Y * zc
     uint32_t zc;        // bins of the last axis
     uint32_t chunks;    // chunks of L columns per batch item
@@ -498,9 +489,9 @@ struct XopArgs {
 };
 
 template <typename R, int RMAX, bool INV, int DIM, bool INPL = false>
-__global__ __launch_bounds__(kBlock) void fft_xop_kernel(GC<R> *__restrict__ spec, GLines a, XopArgs o) {
+__global__ __launch_bounds__(kBlock) void fft_xop_kernel(Cplx<R> *__restrict__ spec, GLines a, XopArgs<R> o) {
     extern __shared__ __align__(16) unsigned char lago_fg[];
-    typedef GC<R> C;
+    typedef Cplx<R> C;
     const int N = a.N, Lp = a.Lp, Lc = o.Lc;
     C *x = reinterpret_cast<C *>(lago_fg), *y = INPL ? x : x + (size_t)Lp * N, *W = y + (size_t)Lp * N;
     const uint32_t n = o.dchunks.div(blockIdx.x);
@@ -520,8 +511,6 @@ __global__ __launch_bounds__(kBlock) void fft_xop_kernel(GC<R> *__restrict__ spe
     // operator: the frequency along the transformed axis = point index (the stages return natural order), the others from
     // the column.  3D: (kx, ky, kz) = (point, column / zc, column % zc); 2D (geometry (1, nx, ny): the transformed axis is
     // the fields' first one, LUT "X"): (point, column)
-    const R *cX = (const R *)o.cosX, *sX = (const R *)o.sinX, *cY = (const R *)o.cosY, *sY = (const R *)o.sinY,
-            *cZ = (const R *)o.cosZ, *sZ = (const R *)o.sinZ;
     const R scale = (R)o.scale;
     for (int i = threadIdx.x; i < N * Lc; i += kBlock) {
         const int kx = (int)o.dLc.div((uint32_t)i), j = i - kx * Lc;
@@ -531,21 +520,19 @@ __global__ __launch_bounds__(kBlock) void fft_xop_kernel(GC<R> *__restrict__ spe
             if constexpr (DIM == 3) {
                 const uint32_t ky = o.dzc.div(col), kz = col - ky * o.zc;
                 FluidBin3<R, INV> op;
-                op.setup(cX[kx], cY[ky], cZ[kz], sX[kx], sY[ky], sZ[kz], o.alpha, o.beta, o.gamma);
+                op.setup(o.op, kx, (int)ky, (int)kz);
                 C A = q[0], B = q[1], Cc = q[2];
-                op.apply(A.re, B.re, Cc.re);
-                op.apply(A.im, B.im, Cc.im);
-                q[0] = C{A.re * scale, A.im * scale};   // scale == 1 is a bitwise no-op (as in the operator kernel)
-                q[1] = C{B.re * scale, B.im * scale};
-                q[2] = C{Cc.re * scale, Cc.im * scale};
+                op.apply(A, B, Cc, scale);
+                q[0] = A;
+                q[1] = B;
+                q[2] = Cc;
             } else {
                 FluidBin2<R, INV> op;
-                op.setup(cX[kx], cY[col], sX[kx], sY[col], o.alpha, o.beta, o.gamma);
+                op.setup(o.op, kx, (int)col);
                 C A = q[0], B = q[1];
-                op.apply(A.re, B.re);
-                op.apply(A.im, B.im);
-                q[0] = C{A.re * scale, A.im * scale};
-                q[1] = C{B.re * scale, B.im * scale};
+                op.apply(A, B, scale);
+                q[0] = A;
+                q[1] = B;
             }
         }
     }
@@ -680,7 +667,7 @@ static BluRef bluestein_table(int N, int M, int sign, hipStream_t s) {
     a.dinner = FastDiv(1u); a.dN = FastDiv((uint32_t)N); a.dL = FastDiv(1u); a.dnhalf = FastDiv((uint32_t)a.nhalf); a.dchunks = FastDiv(1u);
     for (int f = 0, st = 1; f < a.nfac; ++f) { a.ds[f] = FastDiv((uint32_t)st); a.dr[f] = FastDiv((uint32_t)(a.fac[f] + 1) / 2u); st *= a.fac[f]; }
     const size_t smem = (size_t)3 * M * cb;
-    if (launch(bluestein_table_kernel<R>, dim3(1), dim3(kBlock), smem, s, reinterpret_cast<GC<R> *>(t->d), a) != hipSuccess)
+    if (launch(bluestein_table_kernel<R>, dim3(1), dim3(kBlock), smem, s, reinterpret_cast<Cplx<R> *>(t->d), a) != hipSuccess)
         return nullptr;   // (~BluTab frees the buffer)
     if (hipStreamSynchronize(s) != hipSuccess) return nullptr;
     (*g_blu)[key] = t;
@@ -690,7 +677,7 @@ static BluRef bluestein_table(int N, int M, int sign, hipStream_t s) {
 // mode 0: `nlines` complex lines of N points, stride `inner`.  modes 1 / 2: `planes` fields of `nlines` contiguous real
 // lines each (pairs of lines never cross a field: every batch item's result is independent of its neighbours)
 template <typename R>
-static int lines_pass(GC<R> *spec, const R *rin, R *rout, int N, uint64_t inner, uint64_t nlines, uint64_t planes, int sign,
+static int lines_pass(Cplx<R> *spec, const R *rin, R *rout, int N, uint64_t inner, uint64_t nlines, uint64_t planes, int sign,
                       int mode, hipStream_t s) {
     if (N == 1 && mode == 0) return LAGO_OK;
     if (nlines == 0 || planes == 0) return LAGO_OK;
@@ -827,8 +814,7 @@ void tune_generic_fuse(int on) { g_generic_fuse = on ? 1 : 0; }
 // x forward + operator + x inverse in one launch; returns 1 when the length is left to the separate passes (Bluestein
 // lines, lengths whose three-component chunk does not fit the LDS).
 template <typename R>
-static int xop_pass(GC<R> *spec, int inverse, const R *cosX, const R *sinX, const R *cosY, const R *sinY, const R *cosZ,
-                    const R *sinZ, double alpha, double beta, double gamma, int dim, int64_t nn, int64_t X, int64_t Y, int64_t zc,
+static int xop_pass(Cplx<R> *spec, int inverse, const FluidOp<R> &op, int dim, int64_t nn, int64_t X, int64_t Y, int64_t zc,
                     double scale, hipStream_t s) {
     // 3D: lines along X, columns (y, z-bin).  2D (geometry (1, nx, ny)): lines along Y = the fields' first axis, columns z-bin
     const int N = (int)(dim == 3 ? X : Y);
@@ -903,9 +889,9 @@ static int xop_pass(GC<R> *spec, int inverse, const R *cosX, const R *sinX, cons
         r13 = r13 || a.fac[f] == 11 || a.fac[f] == 13;
         odd_small = odd_small || a.fac[f] == 3 || a.fac[f] == 5 || a.fac[f] == 7;
     }
-    XopArgs o;
-    o.cosX = cosX; o.sinX = sinX; o.cosY = cosY; o.sinY = sinY; o.cosZ = cosZ; o.sinZ = sinZ;
-    o.alpha = alpha; o.beta = beta; o.gamma = gamma; o.scale = scale;
+    XopArgs<R> o;
+    o.op = op;
+    o.scale = scale;
     o.cols = (uint32_t)cols;
     o.zc = (uint32_t)zc;
     o.chunks = (uint32_t)((cols + Lc - 1) / Lc);
@@ -934,13 +920,12 @@ static int xop_pass(GC<R> *spec, int inverse, const R *cosX, const R *sinX, cons
 
 // out = irfft(L^(+-2) rfft(m)) through the generic passes; work: the half spectrum (nn * dim * nx * ny * (nz/2 + 1) complex)
 template <typename R>
-int fluid_metric_generic(R *out, const R *m, R *work, int inverse, const R *cosX, const R *sinX, const R *cosY, const R *sinY,
-                         const R *cosZ, const R *sinZ, double alpha, double beta, double gamma, int dim, int64_t nn, int64_t nx,
+int fluid_metric_generic(R *out, const R *m, R *work, int inverse, const FluidOp<R> &op, int dim, int64_t nn, int64_t nx,
                          int64_t ny, int64_t nz, hipStream_t s) {
     // geometry order: 3D (X, Y, Z) = (nx, ny, nz); 2D (X, Y, Z) = (1, nx, ny)
     const int64_t X = dim == 3 ? nx : 1, Y = dim == 3 ? ny : nx, Z = dim == 3 ? nz : ny;
     const int64_t zc = Z / 2 + 1, planes = nn * dim;
-    GC<R> *spec = reinterpret_cast<GC<R> *>(work);
+    Cplx<R> *spec = reinterpret_cast<Cplx<R> *>(work);
     int rc = lines_pass<R>(spec, m, nullptr, (int)Z, 1, (uint64_t)(X * Y), (uint64_t)planes, -1, 1, s);
     if (rc != LAGO_OK) return rc;
     const double scale = 1.0 / ((double)X * (double)Y * (double)Z);
@@ -952,7 +937,7 @@ int fluid_metric_generic(R *out, const R *m, R *work, int inverse, const R *cosX
         if (rc != LAGO_OK) return rc;
     }
     if (g_generic_fuse) {
-        rc = xop_pass<R>(spec, inverse, cosX, sinX, cosY, sinY, cosZ, sinZ, alpha, beta, gamma, dim, nn, X, Y, zc, scale, s);
+        rc = xop_pass<R>(spec, inverse, op, dim, nn, X, Y, zc, scale, s);
         if (rc < 0 || rc > 1) return rc;
         fused = rc == LAGO_OK;
     }
@@ -964,8 +949,7 @@ int fluid_metric_generic(R *out, const R *m, R *work, int inverse, const R *cosX
         rc = lines_pass<R>(spec, nullptr, nullptr, (int)X, (uint64_t)(Y * zc), (uint64_t)(planes * Y * zc), 1, -1, 0, s);
         if (rc != LAGO_OK) return rc;
         const int64_t cx = nx, cy = dim == 2 ? ny / 2 + 1 : ny, cz = dim == 3 ? nz / 2 + 1 : 1;
-        rc = fluid_operator_impl<R>(work, inverse, cosX, sinX, cosY, sinY, cosZ, sinZ, alpha, beta, gamma, dim, nn, cx, cy, cz,
-                                    (void *)s, scale);
+        rc = fluid_operator_impl<R>(work, inverse, op, dim, nn, cx, cy, cz, s, scale);
         if (rc != LAGO_OK) return rc;
         rc = lines_pass<R>(spec, nullptr, nullptr, (int)X, (uint64_t)(Y * zc), (uint64_t)(planes * Y * zc), 1, +1, 0, s);
         if (rc != LAGO_OK) return rc;
@@ -983,11 +967,9 @@ int fluid_metric_generic(R *out, const R *m, R *work, int inverse, const R *cosX
     return finish_launch(s, "fluid_metric");
 }
 
-template int fluid_metric_generic<float>(float *, const float *, float *, int, const float *, const float *, const float *,
-                                         const float *, const float *, const float *, double, double, double, int, int64_t,
-                                         int64_t, int64_t, int64_t, hipStream_t);
-template int fluid_metric_generic<double>(double *, const double *, double *, int, const double *, const double *,
-                                          const double *, const double *, const double *, const double *, double, double,
-                                          double, int, int64_t, int64_t, int64_t, int64_t, hipStream_t);
+template int fluid_metric_generic<float>(float *, const float *, float *, int, const FluidOp<float> &, int, int64_t, int64_t,
+                                         int64_t, int64_t, hipStream_t);
+template int fluid_metric_generic<double>(double *, const double *, double *, int, const FluidOp<double> &, int, int64_t,
+                                          int64_t, int64_t, int64_t, hipStream_t);
 
 }  // namespace lago

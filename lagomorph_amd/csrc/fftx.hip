@@ -14,18 +14,12 @@
 // The operator coefficients (L^2 entries for flat, its Cholesky factor for sharp) depend only on
 // the frequency, not on the batch item; the reference amortises them with a batch loop inside the
 // thread (cuda/metric.cu:272-304).  Here they are tabulated once per (shape, parameters) by
-// fluid_coef_kernel -- same expressions, same roundings as fluid_kernel in metric.hip -- and read
-// back (24 bytes per bin, 3 % of the payload).
-#include "common.hpp"
+// fluid_coef_kernel -- a FluidBin3 of fluid.hpp, stored -- and read back (24 bytes per bin, 3 % of
+// the payload).
+#include "fluid.hpp"
+#include "fft_lds.hpp"   // fl::fluid_bin: a tabulated bin applied
 
 namespace lago {
-
-// cuda/metric.cu:14-18
-__device__ __forceinline__ float fx_safe_sqrt(float x) {
-    if ((double)x < 1e-8) return (float)1e-4;
-    return sqrtf(x);
-}
-__device__ __forceinline__ float fx_recip(float x) { return (float)(1. / (double)x); }
 
 // frequency held at position p of a digit-reversed n-point spectrum, n = R * 2^L2 (fft_lds.hpp: freq_at<Sz<R, L2>>)
 __device__ __forceinline__ int freq_at_rt(int p, int n) {
@@ -38,48 +32,23 @@ __device__ __forceinline__ int freq_at_rt(int p, int n) {
 // One lane per frequency bin (kx, ky, kz): coefficients of cuda/metric.cu:240-270 in the layout
 // tab[bin][6] = {L00 L10 L11 L20 L21 L22} (flat) or {ooG00 G10 ooG11 G20 G21 ooG22} (sharp).
 template <bool INV>
-__global__ __launch_bounds__(kBlock) void fluid_coef_kernel(float *__restrict__ tab, const float *__restrict__ cosX,
-                                                            const float *__restrict__ sinX, const float *__restrict__ cosY,
-                                                            const float *__restrict__ sinY, const float *__restrict__ cosZ,
-                                                            const float *__restrict__ sinZ, double alpha, double beta,
-                                                            double gamma, Geom g, int split) {
+__global__ __launch_bounds__(kBlock) void fluid_coef_kernel(float *__restrict__ tab, FluidOp<float> o, Geom g, int split) {
     const Vox v = locate(g);
     if (!v.valid) return;
     // split layout: (v.j, v.k) are POSITIONS (r, q) of the zy passes' digit-reversed spectrum (fft_lds.hpp), the bin
     // they hold is (freq_at(r), freq_at(q)); the spare column q = nzh is the Nyquist bin
     const int nzh = g.nz - 1;
     const int ky = split ? freq_at_rt(v.j, g.ny) : v.j, kz = split && v.k < nzh ? freq_at_rt(v.k, nzh) : v.k;
-    const float wx = cosX[v.i], wy = cosY[ky], wz = cosZ[kz];
-    const float sx = sinX[v.i], sy = sinY[ky], sz = sinZ[kz];
-    const float lambda = (float)__builtin_fma(alpha, (double)(wx + wy + wz), gamma);
-    const float l00 = (float)__builtin_fma(-beta, (double)wx, (double)lambda);
-    const float l11 = (float)__builtin_fma(-beta, (double)wy, (double)lambda);
-    const float l22 = (float)__builtin_fma(-beta, (double)wz, (double)lambda);
-    const float l10 = (float)(beta * (double)sx * (double)sy);
-    const float l20 = (float)(beta * (double)sx * (double)sz);
-    const float l21 = (float)(beta * (double)sy * (double)sz);
-    const float L00 = lg_fma(l20, l20, lg_fma(l00, l00, l10 * l10));
-    const float L10 = lg_fma(l20, l21, lg_fma(l00, l10, l10 * l11));
-    const float L11 = lg_fma(l21, l21, lg_fma(l10, l10, l11 * l11));
-    const float L20 = lg_fma(l20, l22, lg_fma(l00, l20, l10 * l21));
-    const float L21 = lg_fma(l21, l22, lg_fma(l10, l20, l11 * l21));
-    const float L22 = lg_fma(l22, l22, lg_fma(l20, l20, l21 * l21));
+    FluidBin3<float, INV> op;
+    op.setup(o, v.i, ky, kz);
     // split: [kx][r][q < nzc-1] followed by the Nyquist plane [kx][r] (fft_lds.hpp)
     float *t = !split ? tab + (size_t)v.s * 6
                : v.k < nzh ? tab + (((size_t)v.i * g.ny + v.j) * nzh + v.k) * 6
                            : tab + ((size_t)g.nx * g.ny * nzh + (size_t)v.i * g.ny + v.j) * 6;
-    if (INV) {  // cuda/metric.cu:47-78
-        const float ooG00 = fx_recip(fx_safe_sqrt(L00));
-        const float G10 = L10 * ooG00;
-        const float G20 = L20 * ooG00;
-        float ooG11 = lg_fma(-G10, G10, L11);
-        ooG11 = fx_recip(fx_safe_sqrt(ooG11));
-        const float G21 = lg_fma(-G20, G10, L21) * ooG11;
-        float ooG22 = lg_fma(-G21, G21, lg_fma(-G20, G20, L22));
-        ooG22 = fx_recip(fx_safe_sqrt(ooG22));
-        t[0] = ooG00; t[1] = G10; t[2] = ooG11; t[3] = G20; t[4] = G21; t[5] = ooG22;
+    if (INV) {
+        t[0] = op.ooG00; t[1] = op.G10; t[2] = op.ooG11; t[3] = op.G20; t[4] = op.G21; t[5] = op.ooG22;
     } else {
-        t[0] = L00; t[1] = L10; t[2] = L11; t[3] = L20; t[4] = L21; t[5] = L22;
+        t[0] = op.L00; t[1] = op.L10; t[2] = op.L11; t[3] = op.L20; t[4] = op.L21; t[5] = op.L22;
     }
 }
 
@@ -195,31 +164,11 @@ __global__ __launch_bounds__(256) void fluid_xpass_kernel(float2 *__restrict__ F
         if (act && dbg != 1 && dbg != 2) {
             const uint32_t kx = __brev((uint32_t)p) >> (32 - LOGN);
             const float *t = dbg == 3 ? tab + kc * 6 : tab + (((size_t)kx * ny + y) * nzc + k0 + kc) * 6;
-            const float c0 = t[0], c1 = t[1], c2 = t[2], c3 = t[3], c4 = t[4], c5 = t[5];
             float2 X = buf[(0 * NX + p) * KCP + kc], Y = buf[(1 * NX + p) * KCP + kc], Z = buf[(2 * NX + p) * KCP + kc];
-            float bx[2] = {X.x, X.y}, by[2] = {Y.x, Y.y}, bz[2] = {Z.x, Z.y};
-#pragma unroll
-            for (int q = 0; q < 2; ++q) {
-                float bX = bx[q], bY = by[q], bZ = bz[q];
-                if (INV) {  // cuda/metric.cu:103-130 with (ooG00 G10 ooG11 G20 G21 ooG22) = c0..c5
-                    const float y0 = bX * c0;
-                    const float y1 = lg_fma(-c1, y0, bY) * c2;
-                    const float y2 = lg_fma(-c4, y1, lg_fma(-c3, y0, bZ)) * c5;
-                    bZ = y2 * c5;
-                    bY = lg_fma(-c4, bZ, y1) * c2;
-                    bX = lg_fma(-c3, bZ, lg_fma(-c1, bY, y0)) * c0;
-                } else {  // cuda/metric.cu:145-160 with (L00 L10 L11 L20 L21 L22) = c0..c5
-                    const float x = lg_fma(c3, bZ, lg_fma(c0, bX, c1 * bY));
-                    const float yy = lg_fma(c4, bZ, lg_fma(c1, bX, c2 * bY));
-                    bZ = lg_fma(c5, bZ, lg_fma(c3, bX, c4 * bY));
-                    bX = x;
-                    bY = yy;
-                }
-                bx[q] = bX * scale; by[q] = bY * scale; bz[q] = bZ * scale;
-            }
-            buf[(0 * NX + p) * KCP + kc] = make_float2(bx[0], bx[1]);
-            buf[(1 * NX + p) * KCP + kc] = make_float2(by[0], by[1]);
-            buf[(2 * NX + p) * KCP + kc] = make_float2(bz[0], bz[1]);
+            fl::fluid_bin<INV>(t, X, Y, Z, scale);
+            buf[(0 * NX + p) * KCP + kc] = X;
+            buf[(1 * NX + p) * KCP + kc] = Y;
+            buf[(2 * NX + p) * KCP + kc] = Z;
         }
     }
     __syncthreads();
@@ -232,14 +181,12 @@ __global__ __launch_bounds__(256) void fluid_xpass_kernel(float2 *__restrict__ F
 
 // ---- host side (called from fft.hip) ---------------------------------------------------------
 
-int fluid_coef_launch(float *tab, int inverse, const float *cosX, const float *sinX, const float *cosY,
-                      const float *sinY, const float *cosZ, const float *sinZ, double alpha, double beta,
-                      double gamma, int64_t nx, int64_t ny, int64_t nzc, int split, hipStream_t s) {
+int fluid_coef_launch(float *tab, int inverse, const FluidOp<float> &op, int64_t nx, int64_t ny, int64_t nzc, int split,
+                      hipStream_t s) {
     Geom g;
     if (!make_geom(g, 3, 1, nx, ny, nzc)) return fail_invalid("fluid_coef: bad extent");
     with_flags([&](auto INV) {
-        hipLaunchKernelGGL((fluid_coef_kernel<INV()>), dim3(g.nblocks), dim3(kBlock), 0, s, tab, cosX, sinX, cosY, sinY,
-                           cosZ, sinZ, alpha, beta, gamma, g, split);
+        hipLaunchKernelGGL((fluid_coef_kernel<INV()>), dim3(g.nblocks), dim3(kBlock), 0, s, tab, op, g, split);
     }, inverse != 0);
     return finish_launch(s, "fluid_coef");
 }
