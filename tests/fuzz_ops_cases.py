@@ -21,6 +21,8 @@ interp_bspline, `distance_transform` and `surface_distance` are two families of 
 """
 import numpy as np
 
+from parity_rule import RTOL, bits, close, units   # the project's rule: max|got - ref| <= RTOL max|ref|
+
 # fixed for good: a family's id is part of its cases' streams
 FAMILY_ID = {"jacobian_determinant": 1, "invert_displacement": 2, "gaussian_smooth": 3, "lncc": 4, "joint_histogram": 5,
              "warp_labels": 6, "label_overlap": 7, "distance_transform": 8, "interp_points": 9, "bspline": 10,
@@ -42,7 +44,6 @@ CAPS = {"jacobian_determinant": 100_000, "invert_displacement": 20_000, "gaussia
         "ffd_expand": 40_000, "energy": 100_000, "surface_distance": 6_000, "lncc": 30_000, "bspline": 6_000}
 
 EXTENTS = (1, 2, 3, 5, 8, 16, 17, 32, 33, 63, 64, 65, 70, 128, 130, 256, 257, 300, 513)   # around the tiles of 8, 16, 64, 256, 512
-RTOL = {np.dtype(np.float32): 1e-5, np.dtype(np.float64): 1e-12}   # the project's rule: max|got - ref| <= RTOL max|ref|
 KBLOCK = 256       # common.hpp:27 kBlock
 
 TAGS = {
@@ -119,32 +120,6 @@ def _new(family, seed, index, sp, dtype, N):
             "inputs": {}, "params": {}, "tags": set()}
 
 
-def _close(name, got, want, dtype, fails, worst, scale=None, floor=1e-300):
-    """The project's rule (tests/test_gpu_parity.py, and assert_close / units_of of the families' tests)."""
-    got, want = np.asarray(got, dtype=np.float64), np.asarray(want, dtype=np.float64)
-    if got.shape != want.shape:
-        fails.append(f"{name}: shape {got.shape} vs {want.shape}")
-        return
-    ref = float(np.abs(want).max()) if want.size else 0.0
-    err = float(np.abs(got - want).max()) if got.size else 0.0
-    units = err / (RTOL[np.dtype(dtype)] * max(ref if scale is None else scale, floor))
-    if worst is not None:
-        worst[name] = max(worst.get(name, 0.0), units)
-    if not units <= 1.0:
-        at = np.unravel_index(int(np.nanargmax(np.abs(got - want))), got.shape) if got.size else ()
-        fails.append(f"{name}: max error {err:.3e} = {units:.3g} x {RTOL[np.dtype(dtype)]:.0e} x max|ref| {ref:.3e} at {at}")
-
-
-def _bits(name, got, want, fails):
-    got, want = np.asarray(got), np.asarray(want)
-    if got.shape != want.shape or got.dtype != want.dtype:
-        fails.append(f"{name}: {got.shape} {got.dtype} vs {want.shape} {want.dtype}")
-    elif not np.array_equal(got, want):
-        bad = np.argwhere(got != want)
-        fails.append(f"{name}: not bit-identical in {len(bad)} of {got.size} entries, first at {tuple(int(i) for i in bad[0])}: "
-                     f"{got[tuple(bad[0])]!r} vs {want[tuple(bad[0])]!r}")
-
-
 # ------------------------------------------------------------------ jacobian_determinant  (csrc/diff.hip: jacdet_impl)
 
 def _case_jacobian_determinant(rng, c0):
@@ -187,8 +162,8 @@ def _native_jacobian_determinant(c):
 
 def _judge_jacobian_determinant(c, out, ref, fails, worst):
     """tests/test_gpu_jacdet.py: forward bit for bit, backward within RTOL x max|reference|."""
-    _bits("forward", out["forward"], ref["forward"], fails)
-    _close("backward", out["backward"], ref["backward"], c["dtype"], fails, worst, floor=1e-30)   # (assert_close's own floor)
+    bits(out["forward"], ref["forward"], "forward", fails=fails)
+    close(out["backward"], ref["backward"], c["dtype"], "backward", fails=fails, worst=worst)
 
 
 # ------------------------------------------------------------------ joint_histogram / mi_backward  (csrc/mi.hip)
@@ -299,12 +274,12 @@ def _judge_joint_histogram(c, out, ref, fails, worst):
     """tests/test_gpu_mi.py: P bit for bit (float64), dI and dJ within mi_ref.units <= 1."""
     import mi_ref
 
-    _bits("P", out["P"], ref["P"], fails)
+    bits(out["P"], ref["P"], "P", fails=fails)
     for k in ("dI", "dJ"):
         if out[k].shape != ref[k].shape:
             fails.append(f"{k}: shape {out[k].shape} vs {ref[k].shape}")
             continue
-        u = float(mi_ref.units(out[k], ref[k], c["dtype"].type))
+        u = float(units(out[k], ref[k], c["dtype"]))
         if worst is not None:
             worst[k] = max(worst.get(k, 0.0), u)
         if not u <= 1.0:
@@ -385,7 +360,7 @@ def _ref_warp_labels(c):
 
 def _judge_warp_labels(c, out, ref, fails, worst):
     """tests/test_gpu_labels.py: label for label."""
-    _bits("out", out["out"], ref["out"], fails)
+    bits(out["out"], ref["out"], "out", fails=fails)
 
 
 # ------------------------------------------------------------------ label_overlap  (csrc/labels.hip: label_overlap_impl)
@@ -444,7 +419,7 @@ def _native_label_overlap(c):
 
 def _judge_label_overlap(c, out, ref, fails, worst):
     """tests/test_gpu_labels.py: count for count."""
-    _bits("counts", out["counts"], ref["counts"], fails)
+    bits(out["counts"], ref["counts"], "counts", fails=fails)
 
 
 # ------------------------------------------------------------------ distance_transform  (csrc/edt.hip)
@@ -535,8 +510,8 @@ def _judge_distance_transform(c, out, ref, fails, worst):
         fails.append(f"squared / root: {got.shape} {got.dtype}, {root.shape} {root.dtype} vs float32 {ref['squared'].shape}")
         return
     if "unit_spacing" in c["tags"]:
-        _bits("squared", got, ref["squared"], fails)
-        _bits("root", root.view(np.int32), ref["root"].view(np.int32), fails)
+        bits(got, ref["squared"], "squared", fails=fails)
+        bits(root.view(np.int32), ref["root"].view(np.int32), "root", fails=fails)
         return
     want = ref["_sq64"]
     g64 = got.astype(np.float64)
@@ -642,8 +617,8 @@ def _judge_interp_points(c, out, ref, fails, worst):
     scatter_bound.cell_bound of points_ref.scatter_wide, cells that receive nothing exactly 0."""
     import scatter_bound
 
-    _close("out", out["out"], ref["out"], c["dtype"], fails, worst)
-    _close("d_x", out["d_x"], ref["d_x"], c["dtype"], fails, worst)
+    close(out["out"], ref["out"], c["dtype"], "out", fails=fails, worst=worst)
+    close(out["d_x"], ref["d_x"], c["dtype"], "d_x", fails=fails, worst=worst)
     got = np.asarray(out["d_F"])
     if got.shape != ref["_wide"][0].shape:
         fails.append(f"d_F: shape {got.shape} vs {ref['_wide'][0].shape}")
@@ -764,7 +739,7 @@ def _judge_gaussian_smooth(c, out, ref, fails, worst):
     if out["out"].shape != ref["out"].shape or out["out"].dtype != c["dtype"]:
         fails.append(f"out: {out['out'].shape} {out['out'].dtype} vs {ref['out'].shape} {c['dtype']}")
         return
-    u = float(gauss_ref.units(out["out"], ref["out"], c["dtype"].type))
+    u = float(units(out["out"], ref["out"], c["dtype"]))
     if worst is not None:
         worst["out"] = max(worst.get("out", 0.0), u)
     if not u <= 1.0:
@@ -829,13 +804,13 @@ def _judge_invert_displacement(c, out, ref, fails, worst):
     unfused loop over interp_forward (both come from the device: "rough" and "rough_loop")."""
     allowed = 1.0 if c["params"]["iters"] <= 1 else 2.0
     w = {}
-    _close("v", out["v"], ref["v"], c["dtype"], [], w)
+    close(out["v"], ref["v"], c["dtype"], "v", fails=[], worst=w)
     if "v" not in w or not w["v"] <= allowed:
         fails.append(f"v: {w.get('v')} x RTOL x max|ref| (allowed {allowed:g})")
     if worst is not None and "v" in w:
         worst["v"] = max(worst.get("v", 0.0), w["v"] / allowed)
-    _close("lam", out["lam"], ref["lam"], c["dtype"], fails, worst)
-    _bits("rough", out["rough"], out["rough_loop"], fails)
+    close(out["lam"], ref["lam"], c["dtype"], "lam", fails=fails, worst=worst)
+    bits(out["rough"], out["rough_loop"], "rough", fails=fails)
 
 
 # ------------------------------------------------------------------ ffd_expand and its adjoint  (csrc/ffd.hip)
@@ -1135,7 +1110,7 @@ def _case_lncc(rng, c0):
         J = J.astype(np.float32)
         ref = lncc_ref.lncc_with_grads(I, J, g, sigma, mode=mode)
         emu = lncc_ref.emulate(dtype.type)(I, J, g, sigma, mode=mode)
-        if max(lncc_ref.units(a, b, dtype.type) for a, b in zip(emu, ref)) <= 0.5:
+        if max(units(a, b, dtype) for a, b in zip(emu, ref)) <= 0.5:
             break
     else:
         raise RuntimeError("lncc: 64 draws without a well-conditioned case")
@@ -1187,7 +1162,7 @@ def _judge_lncc(c, out, ref, fails, worst):
         if out[k].shape != ref[k].shape or out[k].dtype != c["dtype"]:
             fails.append(f"{k}: {out[k].shape} {out[k].dtype}")
             continue
-        u = float(lncc_ref.units(out[k], ref[k], c["dtype"].type))
+        u = float(units(out[k], ref[k], c["dtype"]))
         if worst is not None:
             worst[k] = max(worst.get(k, 0.0), u)
         if not u <= 1.0:
@@ -1260,7 +1235,7 @@ def _judge_bspline(c, out, ref, fails, worst):
     import bspline_ref
 
     for k in ("prefilter", "values", "d_u"):
-        _close(k, out[k], ref[k], c["dtype"], fails, worst)
+        close(out[k], ref[k], c["dtype"], k, fails=fails, worst=worst)
     tp = bspline_ref.taps(c["inputs"]["u"], c["params"]["dt"])
     if out["d_u"].shape == ref["d_u"].shape:
         for a in range(len(c["sp"])):

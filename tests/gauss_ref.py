@@ -8,16 +8,6 @@ import numbers
 import numpy as np
 
 MAX_RADIUS = 32
-RTOL = {np.float32: 1e-5, np.float64: 1e-12}   # the project's rule: max|got - ref| <= RTOL max|ref|
-
-
-def units(got, want, dtype, scale=None):
-    """max |got - want| in units of RTOL[dtype] x max|want| (or x scale), for numpy arrays."""
-    got, want = np.asarray(got).astype(np.float64), np.asarray(want, dtype=np.float64)
-    assert got.shape == want.shape, f"shape {got.shape} vs {want.shape}"
-    ref = np.abs(want).max() if scale is None else scale
-    err = np.abs(got - want).max() if got.size else 0.0
-    return err / (RTOL[dtype] * max(ref, 1e-300))
 
 
 def radius(sigma, truncate=4.0):

@@ -11,8 +11,6 @@ import numpy as np
 
 import gauss_ref
 
-RTOL = {np.float32: 1e-5, np.float64: 1e-12}   # the project's rule: max|got - ref| <= RTOL max|ref|
-
 
 _MATRICES = {}
 
@@ -78,14 +76,6 @@ def emulate(dtype):
     def run(I, J, g, sigma, truncate=4.0, mode="wrap", eps=1e-5):
         return _compute(I, J, g, sigma, truncate, mode, eps, dtype)
     return run
-
-
-def units(got, want, dtype):
-    """max|got - want| in units of RTOL[dtype] max|want|."""
-    got, want = np.asarray(got, dtype=np.float64), np.asarray(want, dtype=np.float64)
-    assert got.shape == want.shape, f"shape {got.shape} vs {want.shape}"
-    err = np.abs(got - want).max() if got.size else 0.0
-    return err / (RTOL[dtype] * max(np.abs(want).max() if want.size else 0.0, 1e-300))
 
 
 # ---- the cases tests/test_lncc_host.py (as a condition on the inputs) and tests/test_gpu_lncc.py (on the device) share

@@ -19,17 +19,8 @@ Per image with range (lo, hi) and B bins, in double and in exactly this order (n
 tests/test_mi_host.py holds the gradient against central differences and the C++ header against the integers here."""
 import numpy as np
 
-RTOL = {np.float32: 1e-5, np.float64: 1e-12}   # the project's rule: max|got - ref| <= RTOL max|ref|
 ONE = 4294967296.0                              # 2^32
 EPS = 1e-10
-
-
-def units(got, want, dtype):
-    """max|got - want| in units of RTOL[dtype] max|want|."""
-    got, want = np.asarray(got, dtype=np.float64), np.asarray(want, dtype=np.float64)
-    assert got.shape == want.shape, f"shape {got.shape} vs {want.shape}"
-    err = np.abs(got - want).max() if got.size else 0.0
-    return err / (RTOL[dtype] * max(np.abs(want).max() if want.size else 0.0, 1e-300))
 
 
 def window(v, rng, B):

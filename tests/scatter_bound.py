@@ -116,8 +116,3 @@ def assert_cells(got, wide, dtype, what, start=None, ref=None):
         raise AssertionError(msg)
     return ratio
 
-
-def maxnorm_units(got, want, rtol):
-    """The suite's older criterion: max |got - want| in units of rtol * max |want| (accepted when <= 1)."""
-    got, want = np.asarray(got, dtype=np.float64), np.asarray(want, dtype=np.float64)
-    return float(np.abs(got - want).max() / (rtol * max(float(np.abs(want).max()), 1e-30)))

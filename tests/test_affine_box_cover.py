@@ -10,27 +10,21 @@ out, on both sides of every threshold of affine_item_regular, and that a deliber
 LAGO_BOX_MARGIN_REPORT=<file>: the per-case figures as JSON (profiles/affine_box_margin.md is made from it)."""
 import json
 import os
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
 import affine_box_cases as cases
+import native_build
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-pytestmark = pytest.mark.skipif(shutil.which("hipcc") is None, reason="hipcc not available")
+pytestmark = native_build.needs_hipcc
 
 REPORT = {}
 
 
 def _build(tmp, name, extra=()):
-    exe = str(tmp / name)
-    src = os.path.join(HERE, "native", "affine_box_emul.hip")
-    # -ffp-contract=off as the library itself is built (lagomorph_amd/build.py): the double expressions keep their order
-    subprocess.run(["hipcc", "-O2", "-std=c++17", "-ffp-contract=off", "-pthread", "--offload-arch=gfx950", *extra, "-o", exe, src],
-                   check=True, timeout=600)
-    return exe
+    return native_build.build(tmp, "affine_box_emul.hip", wall=False, werror=False, extra=("-pthread", *native_build.GFX950, *extra),
+                              compiler="hipcc", name=name)
 
 
 @pytest.fixture(scope="module")
@@ -53,8 +47,7 @@ def walk(exe, tmp, rows, dtype=np.float32):
         for name, shape, A, T in rows:
             vals = [_num(v, dtype) for v in np.asarray(A).reshape(-1)] + [_num(v, dtype) for v in np.asarray(T).reshape(-1)]
             f.write(" ".join([name, "f32" if dtype == np.float32 else "f64", *map(str, shape), *vals]) + "\n")
-    r = subprocess.run([exe, path], capture_output=True, text=True, timeout=1800)
-    assert r.returncode == 0, r.stdout + r.stderr
+    r = native_build.run(exe, path, timeout=1800)
     out = {}
     for line in r.stdout.splitlines():
         p = line.split()

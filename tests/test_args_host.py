@@ -15,24 +15,15 @@ header with a plain C++17 compiler, stubs fail_invalid so that the message is re
   * any_overlap for two outputs and two inputs, pointers 0..12 (0: null) and sizes 0..4 bytes, every combination against
     the sets of byte addresses; a null or empty span never causes a rejection;
   * check_gather's byte counts, null and overlap rules on a few hand-made layouts."""
-import os
 import re
-import shutil
-import subprocess
 
-import pytest
+import native_build
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-CXX = next((c for c in ("c++", "g++", "clang++", "hipcc") if shutil.which(c)), None)
-pytestmark = pytest.mark.skipif(CXX is None, reason="no C++ compiler available")
+pytestmark = native_build.needs_cxx_or_hipcc
 
 
 def test_volume_geom_and_overlap_rules_against_wide_references(tmp_path):
-    exe = str(tmp_path / "args_emul")
-    src = os.path.join(HERE, "native", "args_emul.cpp")
-    lang = ["-x", "c++"] if CXX == "hipcc" else []   # (as host code only: this part of the header needs no HIP)
-    subprocess.run([CXX, "-O1", "-std=c++17", "-Wall", "-Werror", *lang, "-o", exe, src], check=True, timeout=600)
-    r = subprocess.run([exe], capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, r.stdout + r.stderr
+    # (as host code only: this part of the header needs no HIP)
+    r = native_build.run(native_build.build(tmp_path, "args_emul.cpp", "-O1", fp_contract_off=False, compiler=native_build.CXX_OR_HIPCC))
     m = re.search(r"(\d+) checks, 0 failed", r.stdout)
     assert m and int(m.group(1)) > 17_000_000, r.stdout

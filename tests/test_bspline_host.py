@@ -12,9 +12,7 @@
 - the public surface: names, C symbols, the argument errors (raised on CPU tensors, before any device call)."""
 import ctypes
 import os
-import shutil
 import struct
-import subprocess
 
 import numpy as np
 import pytest
@@ -22,9 +20,9 @@ import torch
 
 import bspline_ref as ref
 import labels_ref
+import native_build
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-CXX = next((c for c in ("c++", "g++", "clang++") if shutil.which(c)), None)
 SHAPES = ((2, 3, 5), (5, 4, 7), (9, 11), (1, 6, 3), (2, 2))
 KINDS = ("random", "shift_out", "half", "huge", "nonfinite")
 
@@ -160,17 +158,14 @@ def _emul_cases():
 
 
 def _run_emul(tmp_path, name, extra=()):
-    exe, src, dst = str(tmp_path / name), str(tmp_path / "cases.bin"), str(tmp_path / "out.bin")
-    # -ffp-contract=off as the library itself is built (lagomorph_amd/build.py)
-    subprocess.run([CXX, "-O2", "-std=c++17", "-ffp-contract=off", "-Wall", "-Werror", *extra, "-o", exe,
-                    os.path.join(HERE, "native", "bspline_emul.cpp")], check=True, timeout=600)
+    src, dst = str(tmp_path / "cases.bin"), str(tmp_path / "out.bin")
+    exe = native_build.build(tmp_path, "bspline_emul.cpp", extra=extra, name=name)
     cases = _emul_cases()
     with open(src, "wb") as f:
         for dtype, n, x in cases:
             f.write(struct.pack("<3i", np.dtype(dtype).itemsize, n, x.size))
             f.write(x.tobytes())
-    r = subprocess.run([exe, src, dst], capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0 and not r.stderr.strip(), (r.returncode, r.stdout, r.stderr[-2000:])
+    native_build.run(exe, src, dst, quiet=True)
     raw, at = open(dst, "rb").read(), 0
     for dtype, n, x in cases:
         ints = np.frombuffer(raw, dtype="<i4", count=x.size * 6, offset=at).reshape(-1, 6)
@@ -214,12 +209,12 @@ def _check_emul(results):
     assert seen > 5000
 
 
-@pytest.mark.skipif(CXX is None, reason="no C++ compiler available")
+@native_build.needs_cxx
 def test_header_emulation_equals_the_reference_exactly(tmp_path):
     _check_emul(_run_emul(tmp_path, "bspline_emul"))
 
 
-@pytest.mark.skipif(CXX is None, reason="no C++ compiler available")
+@native_build.needs_cxx
 def test_header_emulation_under_the_sanitizers(tmp_path):
     """The same stand-alone host program with AddressSanitizer and UndefinedBehaviorSanitizer: the conversions of
     out-of-range, infinite and NaN positions stay defined."""

@@ -13,14 +13,7 @@ tests/native/chunk_table_emul.cpp runs the header's host part with a plain C++17
     misaligned differently get no vector at all.
 
 The two scratch queries of the C ABI answer the same restatement on the same grid."""
-import os
-import shutil
-import subprocess
-
-import pytest
-
-HERE = os.path.dirname(os.path.abspath(__file__))
-CXX = next((c for c in ("c++", "g++", "clang++") if shutil.which(c)), None)
+import native_build
 
 SLAB = 8 << 20
 MI_CHUNK, LABELS_CHUNK = 4096, 16384   # kMiChunkMin of mi.hip, LAGO_LABELS_CHUNK of labels.hip
@@ -58,10 +51,7 @@ def overlap_split_before(table_bytes, rows, nvox, scratch_chunks):
 
 
 def _build(tmp_path, name, extra=()):
-    exe = str(tmp_path / name)
-    subprocess.run([CXX, "-O1", "-std=c++17", "-Wall", "-Werror", *extra, "-o", exe,
-                    os.path.join(HERE, "native", "chunk_table_emul.cpp")], check=True, timeout=600)
-    return exe
+    return native_build.build(tmp_path, "chunk_table_emul.cpp", "-O1", fp_contract_off=False, extra=extra, name=name)
 
 
 def _cases():
@@ -73,8 +63,7 @@ def _cases():
 def _run(exe):
     split, walk = _cases()
     text = "".join("C %d %d %d %d %d\n" % c for c in split) + "".join("W %d %d %d %d\n" % c for c in walk)
-    r = subprocess.run([exe], input=text, capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0 and not r.stderr.strip(), (r.returncode, r.stderr[-2000:])
+    r = native_build.run(exe, stdin=text, quiet=True)
     out = [tuple(int(x) for x in line.split()) for line in r.stdout.splitlines()]
     assert len(out) == len(split) + len(walk)
     return split, out[:len(split)], walk, out[len(split):]
@@ -114,12 +103,12 @@ def _check(split, got_split, walk, got_walk):
     assert vectors > 500
 
 
-@pytest.mark.skipif(CXX is None, reason="no C++ compiler available")
+@native_build.needs_cxx
 def test_header_arithmetic_equals_the_formulas_it_replaced(tmp_path):
     _check(*_run(_build(tmp_path, "chunk_table_emul")))
 
 
-@pytest.mark.skipif(CXX is None, reason="no C++ compiler available")
+@native_build.needs_cxx
 def test_header_arithmetic_under_the_sanitizers(tmp_path):
     """The same stand-alone host program with AddressSanitizer and UndefinedBehaviorSanitizer: no division by zero for an
     empty row, no overflow at 2^31 - 1 rows of 2^30 voxels."""

@@ -10,18 +10,16 @@
 - the public surface: names, the C symbol, and the argument errors (raised on CPU tensors, before any device call)."""
 import ctypes
 import os
-import shutil
 import struct
-import subprocess
 
 import numpy as np
 import pytest
 import torch
 
 import edt_ref as ref
+import native_build
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-CXX = next((c for c in ("c++", "g++", "clang++") if shutil.which(c)), None)
 SHAPES = ((5, 6, 7), (7, 9), (1, 9), (2, 2, 2))
 SPACING = (1.5, 0.7, 2.0)
 REL = 8 * 2.0 ** -24   # float32 against the real value: one rounding for s delta, one for the square, one per addition
@@ -128,11 +126,7 @@ def test_signed_distance_of_a_box():
 # ---- the header against the reference
 
 def _build_emul(tmp_path, name, extra=()):
-    exe = str(tmp_path / name)
-    # -ffp-contract=off as the library itself is built (lagomorph_amd/build.py)
-    subprocess.run([CXX, "-O2", "-std=c++17", "-ffp-contract=off", "-Wall", "-Werror", *extra, "-o", exe,
-                    os.path.join(HERE, "native", "edt_emul.cpp")], check=True, timeout=600)
-    return exe
+    return native_build.build(tmp_path, "edt_emul.cpp", extra=extra, name=name)
 
 
 def _emul_cases(shapes):
@@ -154,8 +148,7 @@ def _run_emul(exe, tmp_path, cases):
             s3 = (1.0,) * (3 - len(sp)) + ((s,) * len(sp) if np.ndim(s) == 0 else tuple(s))
             f.write(struct.pack("<7i3f", len(sp), L.shape[0], *n, code, label, *s3))
             f.write(np.ascontiguousarray(L, dtype="<i4").tobytes())
-    r = subprocess.run([exe, src, dst], capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0 and not r.stderr.strip(), (r.returncode, r.stdout, r.stderr[-2000:])
+    native_build.run(exe, src, dst, quiet=True)
     raw, at = open(dst, "rb").read(), 0
     for sp, L, where, code, label, s in cases:
         feat = np.frombuffer(raw, dtype="<i4", count=L.size, offset=at).reshape(L.shape)
@@ -182,7 +175,7 @@ def _check_emul(cases, results):
     return exact
 
 
-@pytest.mark.skipif(CXX is None, reason="no C++ compiler available")
+@native_build.needs_cxx
 def test_header_emulation_equals_the_reference(tmp_path):
     cases = list(_emul_cases(SHAPES + ((8, 16, 32), (1, 5, 4), (6, 1, 3), (33, 9, 10), (3, 70))))
     assert len(cases) > 400
@@ -190,7 +183,7 @@ def test_header_emulation_equals_the_reference(tmp_path):
     assert exact == len(cases) // 2
 
 
-@pytest.mark.skipif(CXX is None, reason="no C++ compiler available")
+@native_build.needs_cxx
 def test_header_emulation_under_the_sanitizers(tmp_path):
     """The same stand-alone host program with AddressSanitizer and UndefinedBehaviorSanitizer: the clamped neighbour
     indices of the surface stencil stay inside the label map at every border, thin extents included."""

@@ -12,18 +12,16 @@
 import ctypes
 import itertools
 import os
-import shutil
 import struct
-import subprocess
 
 import numpy as np
 import pytest
 import torch
 
 import energy_ref as ref
+import native_build
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-CXX = next((c for c in ("c++", "g++", "clang++") if shutil.which(c)), None)
 shapes = pytest.mark.parametrize("shape", ref.HOST_SHAPES, ids=str)
 kinds = pytest.mark.parametrize("kind", ref.KINDS)
 spacings = pytest.mark.parametrize("spacing", ref.SPACINGS, ids=str)
@@ -158,7 +156,7 @@ def _cases():
 
 
 def _run_emul(tmp_path, name, cases, extra=()):
-    exe, src, dst = str(tmp_path / name), str(tmp_path / "in.bin"), str(tmp_path / "out.bin")
+    src, dst = str(tmp_path / "in.bin"), str(tmp_path / "out.bin")
     with open(src, "wb") as f:
         f.write(struct.pack("<i", len(cases)))
         for k, shape, spacing, dtype, u, affine in cases:
@@ -167,11 +165,7 @@ def _run_emul(tmp_path, name, cases, extra=()):
             h = (1.0,) * (3 - d) + ref.spacing_tuple(spacing, d)
             f.write(struct.pack("<6i3d", k, d, *n, np.dtype(dtype).itemsize, *h))
             f.write(u.tobytes())
-    # -ffp-contract=off as the library itself is built (lagomorph_amd/build.py)
-    subprocess.run([CXX, "-O2", "-std=c++17", "-ffp-contract=off", "-Wall", "-Werror", *extra, "-o", exe,
-                    os.path.join(HERE, "native", "energy_emul.cpp")], check=True, timeout=600)
-    r = subprocess.run([exe, src, dst], capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0 and not r.stderr.strip(), (r.returncode, r.stdout, r.stderr[-2000:])
+    native_build.run(native_build.build(tmp_path, "energy_emul.cpp", extra=extra, name=name), src, dst, quiet=True)
     return open(dst, "rb").read()
 
 
@@ -195,13 +189,13 @@ def _check_emul(raw, cases):
     assert at == len(raw)
 
 
-@pytest.mark.skipif(CXX is None, reason="no C++ compiler available")
+@native_build.needs_cxx
 def test_header_emulation_equals_the_reference(tmp_path):
     cases = _cases()
     _check_emul(_run_emul(tmp_path, "energy_emul", cases), cases)
 
 
-@pytest.mark.skipif(CXX is None, reason="no C++ compiler available")
+@native_build.needs_cxx
 def test_header_emulation_under_the_sanitizers(tmp_path):
     """The same stand-alone host program with AddressSanitizer and UndefinedBehaviorSanitizer."""
     cases = _cases()

@@ -12,17 +12,15 @@
   call) and the C entry points' validation with pointers that are never dereferenced."""
 import ctypes
 import os
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 import torch
 
 import ffd_ref as ref
+import native_build
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-CXX = next((c for c in ("c++", "g++", "clang++") if shutil.which(c)), None)
 PAIRS = ((5, 2), (6, 3), (7, 4), (3, 8), (9, 4), (11, 1), (1, 5), (70, 5), (41, 7))
 
 
@@ -75,12 +73,8 @@ def test_reference_adjoint_identity(shape, spacing):
 # ---- the header against the reference
 
 def _run_emul(tmp_path, name, extra=()):
-    exe, dst = str(tmp_path / name), str(tmp_path / "out.bin")
-    # -ffp-contract=off as the library itself is built (lagomorph_amd/build.py)
-    subprocess.run([CXX, "-O2", "-std=c++17", "-ffp-contract=off", "-Wall", "-Werror", *extra, "-o", exe,
-                    os.path.join(HERE, "native", "ffd_emul.cpp")], check=True, timeout=600)
-    r = subprocess.run([exe, dst], capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0 and not r.stderr.strip(), (r.returncode, r.stdout, r.stderr[-2000:])
+    dst = str(tmp_path / "out.bin")
+    native_build.run(native_build.build(tmp_path, "ffd_emul.cpp", extra=extra, name=name), dst, quiet=True)
     return open(dst, "rb").read()
 
 
@@ -111,12 +105,12 @@ def _check_emul(raw):
         assert np.array_equal(m[s - 1], (np.arange(1, 201) - 1) // s + 4)
 
 
-@pytest.mark.skipif(CXX is None, reason="no C++ compiler available")
+@native_build.needs_cxx
 def test_header_emulation_equals_the_reference_exactly(tmp_path):
     _check_emul(_run_emul(tmp_path, "ffd_emul"))
 
 
-@pytest.mark.skipif(CXX is None, reason="no C++ compiler available")
+@native_build.needs_cxx
 def test_header_emulation_under_the_sanitizers(tmp_path):
     """The same stand-alone host program with AddressSanitizer and UndefinedBehaviorSanitizer."""
     _check_emul(_run_emul(tmp_path, "ffd_emul_san", ("-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all")))

@@ -22,8 +22,8 @@ import torch
 
 import affine_box_cases as cases
 import affine_ref as ref
+from gpu_util import DTYPES, OBSERVED, assert_close, dev, host
 from oracle import lago_oracle as orc
-from test_gpu_parity import DTYPES, OBSERVED, assert_close, dev, host
 
 pytestmark = pytest.mark.gpu
 

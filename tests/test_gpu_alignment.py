@@ -20,6 +20,7 @@ Each case of the table below is one call with its tensor arguments, its referenc
     is off, no change otherwise.
 
 Shapes are the smallest that reach each path (tests/test_gpu_launch_arms.py, tests/test_gpu_dispatch.py)."""
+import functools
 import inspect
 import itertools
 import json
@@ -33,6 +34,7 @@ import bspline_ref
 import edt_ref
 import ffd_ref
 import gauss_ref
+import gpu_util
 import invert_ref
 import jacdet_ref
 import labels_ref
@@ -41,9 +43,10 @@ import mi_ref
 import points_ref
 from offset_views import OFFSETS, margins_intact, offset_view, poisoned
 from oracle import lago_oracle as orc
-from test_gpu_parity import OBSERVED, _disp, assert_bits, assert_close, dev, host, rnd
+from gpu_util import OBSERVED, assert_close, dev, displacement, host, rnd
 
 pytestmark = pytest.mark.gpu
+assert_bits = functools.partial(gpu_util.assert_bits, check_dtype=False)   # these sites compare shape and bits, as they always did
 
 F32, F64 = torch.float32, torch.float64
 BOTH = (F32, F64)
@@ -225,7 +228,7 @@ def _fixed(f32=None, f64=None):
 def _interp_inputs(sp, nc, bc, smooth, seed):
     def make(dtype, ext):
         rng = _seed(1, seed, *sp)
-        u = rnd(rng, (2, len(sp)) + sp, dtype, 0.5) if smooth else _disp(rng, 2, sp, dtype)
+        u = rnd(rng, (2, len(sp)) + sp, dtype, 0.5) if smooth else displacement(rng, 2, sp, dtype)
         return {"I": rnd(rng, ((1 if bc else 2), nc) + sp, dtype), "u": u, "go": rnd(rng, (2, nc) + sp, dtype)}
     return make
 
@@ -291,7 +294,7 @@ for sp, bc, path in (((5, 6, 7), False, None), ((7, 9), True, None), ((16, 16, 1
 for sp in ((9, 8), (128, 128)):
     def make(dtype, ext, sp=sp):
         rng = _seed(6, *sp)
-        return {"I": rnd(rng, (2, 3) + sp, dtype), "u": _disp(rng, 2, sp, dtype)}
+        return {"I": rnd(rng, (2, 3) + sp, dtype), "u": displacement(rng, 2, sp, dtype)}
     add(f"interp_hessian_diagonal_image {sp}", ["interp_hessian_diagonal_image"], make,
         lambda ext, t: {"out": ext.interp_hessian_diagonal_image(t["I"], t["u"], 0.6)},
         lambda a: {"out": orc.interp_hessian_diagonal_image(a["I"], a["u"], 0.6)}, {"out": "close"})
@@ -306,7 +309,7 @@ def _fields_make(sp, names, seed, first_scale=None, with_out=False):
         a = {}
         for i, n in enumerate(names):
             if i == 0 and first_scale is None:
-                a[n] = _disp(rng, 2, sp, dtype)
+                a[n] = displacement(rng, 2, sp, dtype)
             else:
                 a[n] = rnd(rng, (2, len(sp)) + sp, dtype, first_scale if i == 0 else 1.0)
         if with_out:

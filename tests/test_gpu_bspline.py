@@ -12,37 +12,26 @@ lines up to n = 40 (float32) / 20 (float64), 128 up to 80 / 40 and 64 beyond, so
 passes end at n = 256 in both types (csrc/bspline.hip: kBsStagedMax): 256 on each axis in turn is the largest LDS
 tile (128 KiB in float64), 257 and 700 on each axis in turn, in thin volumes, run the long-line path through global
 memory.  Rows N * C in {1, 3, 70}: 70 rows of (5, 6, 7) are several workgroups of every pass."""
+import functools
+
 import numpy as np
 import pytest
 import torch
 
 import bspline_ref as ref
 import labels_ref
+from gpu_util import assert_close, dev, host
 
 pytestmark = pytest.mark.gpu
 
 N = 2
-RTOL = {np.dtype(np.float32): 1e-5, np.dtype(np.float64): 1e-12}
+_close = functools.partial(assert_close, floor=0, record=False)   # the bound is RTOL * max|want| exactly: no floor under a zero reference
 both_dtypes = pytest.mark.parametrize("dtype", [np.float32, np.float64], ids=["f32", "f64"])
 KINDS = ("random", "shift_out", "half", "huge", "nonfinite")
 GENERAL = ((5, 6, 7), (7, 9))
 SMALL = ((1, 5, 4), (6, 1, 3), (2, 2, 2), (2, 2), (1, 9))
 EDGES = tuple((3, 4, n) for n in (63, 64, 65)) + tuple((3, n, 4) for n in (63, 65)) + ((65, 3, 4), (63, 5), (5, 65))
 LONG = tuple(s for n in (256, 257, 700) for s in ((n, 2, 3), (2, n, 3), (2, 3, n), (n, 3), (3, n)))
-
-
-def _dev(x):
-    return torch.from_numpy(np.ascontiguousarray(x)).cuda()
-
-
-def _host(x):
-    return x.detach().cpu().numpy()
-
-
-def _close(got, want, dtype, what):
-    got = _host(got).astype(np.float64)
-    err, tol = np.abs(got - want).max(), RTOL[np.dtype(dtype)] * np.abs(want).max()
-    assert err <= tol, f"{what}: max error {err:.3e} over {tol:.3e}"
 
 
 def _channels(sp):
@@ -56,13 +45,13 @@ def _prefilter_case(sp, rows, dtype):
 
     n, c = {1: (1, 1), 3: (1, 3), 70: (7, 10)}[rows]
     I = ref.image(n, c, sp, dtype, seed=rows)
-    Id = _dev(I)
+    Id = dev(I)
     for adjoint in (False, True):
         got = lm.bspline_prefilter(Id, adjoint=adjoint)
         assert got.shape == Id.shape and got.dtype == Id.dtype
         _close(got, ref.prefilter(I, adjoint), dtype, f"prefilter {sp} rows {rows} adjoint {adjoint}")
         assert torch.equal(got, lm.bspline_prefilter(Id, adjoint=adjoint))   # no atomics: the same bits
-    assert torch.equal(Id, _dev(I))   # the input is left alone
+    assert torch.equal(Id, dev(I))   # the input is left alone
 
 
 @both_dtypes
@@ -93,13 +82,13 @@ def test_round_trip_and_adjoint_identity(sp, dtype):
 
     d = len(sp)
     I = ref.image(N, 3, sp, dtype)
-    Id = _dev(I)
+    Id = dev(I)
     zero = torch.zeros((N, d) + sp, dtype=Id.dtype, device="cuda")
     _close(lm.interp_cubic(Id, zero), I.astype(np.float64), dtype, f"interp_cubic(I, 0) {sp}")
     _close(lm.interp_cubic(Id[:1].contiguous(), zero), np.broadcast_to(I[:1], I.shape).astype(np.float64), dtype, f"broadcast {sp}")
     if dtype == np.float64:
         g = ref.image(N, 3, sp, dtype, seed=1)
-        gd = _dev(g)
+        gd = dev(g)
         lhs = float((lm.bspline_prefilter(Id) * gd).sum())
         rhs = float((Id * lm.bspline_prefilter(gd, adjoint=True)).sum())
         scale = float((lm.bspline_prefilter(Id).abs() * gd.abs()).sum())
@@ -127,14 +116,14 @@ def test_forward_and_position_gradient(sp, dtype):
                 out |= x[3]
             assert out.any() and (min(sp) < 3 or not out.all()), sp
         assert nan.any() == (kind == "nonfinite")
-        ud = _dev(u)
+        ud = dev(u)
         for K in _channels(sp):
             Cf = ref.image(N, K, sp, dtype, seed=K)
             go = ref.image(N, K, sp, dtype, seed=100 + K)
-            god = _dev(go)
+            god = dev(go)
             for bc in (False, True):
                 Ch = Cf[:1] if bc else Cf
-                Cd = _dev(Ch)
+                Cd = dev(Ch)
                 for dt in ((1.0, -0.7) if kind == "random" and not bc else (1.0,)):
                     if dt != 1.0:
                         assert not np.isnan(u).any()
@@ -143,14 +132,14 @@ def test_forward_and_position_gradient(sp, dtype):
                     ug = ud.clone().requires_grad_(True)
                     got = lm.interp_bspline(Cd, ug, dt)
                     assert got.shape == (N, K) + sp and got.dtype == Cd.dtype
-                    gh = _host(got)
+                    gh = host(got)
                     if dt == 1.0:   # NaN exactly where a coordinate is NaN
                         assert np.array_equal(np.isnan(gh), np.broadcast_to(nan[:, None], gh.shape)), what
                     ok = ~np.isnan(want)
                     _close(torch.from_numpy(np.where(ok, gh, 0)), np.where(ok, want, 0), dtype, "values " + what)
                     got.backward(god)
                     du_want = ref.grad_u(go, Ch.astype(np.float64), u, dt)
-                    du = _host(ug.grad)
+                    du = host(ug.grad)
                     assert np.array_equal(np.isnan(du), np.isnan(du_want)), what
                     okd = ~np.isnan(du_want)
                     _close(torch.from_numpy(np.where(okd, du, 0)), np.where(okd, du_want, 0), dtype, "d_u " + what)
@@ -197,18 +186,18 @@ def test_coefficient_gradient_cell_by_cell(sp, dtype):
     worst = 0.0
     for kind in KINDS:
         u = labels_ref.displacement(kind, N, sp, dtype)
-        ud = _dev(u)
+        ud = dev(u)
         for K in _channels(sp):
             go = ref.image(N, K, sp, dtype, seed=7)
-            god = _dev(go)
+            god = dev(go)
             for bc in (False, True):
                 what = f"{sp} {kind} K {K} bc {bc}"
                 shape = (1 if bc else N, K) + sp
-                Cd = _dev(ref.image(shape[0], K, sp, dtype, seed=9))
+                Cd = dev(ref.image(shape[0], K, sp, dtype, seed=9))
                 wide = ref.grad_C_wide(go, shape, u, **wide_kw)
                 d_C, d_u = ext.interp_bspline_backward(god, Cd, ud, 1.0, True, False)
                 assert d_u is None and d_C.shape == shape
-                ratio, empty_ok = ref.cell_ratio(_host(d_C), wide, dtype, d)
+                ratio, empty_ok = ref.cell_ratio(host(d_C), wide, dtype, d)
                 assert empty_ok, what
                 assert ratio <= 1.0, f"{what}: worst cell at {ratio:.3f} of its bound"
                 worst = max(worst, ratio)
@@ -231,9 +220,9 @@ def test_gradcheck(sp):
     # positions at least 0.1 voxel inside the grid: i + u in [0.1, n - 1.1]
     idx = np.indices(sp).astype(np.float64)
     target = np.stack([rng.uniform(0.1, n - 1.1, (N,) + sp) for n in sp], 1)
-    u = _dev(target - idx[None]).requires_grad_(True)
-    I = _dev(ref.image(N, 2, sp, np.float64)).requires_grad_(True)
-    I1 = _dev(ref.image(1, 2, sp, np.float64)).requires_grad_(True)
+    u = dev(target - idx[None]).requires_grad_(True)
+    I = dev(ref.image(N, 2, sp, np.float64)).requires_grad_(True)
+    I1 = dev(ref.image(1, 2, sp, np.float64)).requires_grad_(True)
     kw = dict(eps=1e-6, atol=1e-6, rtol=1e-6, nondet_tol=1e-9)
     assert torch.autograd.gradcheck(lambda x: lm.bspline_prefilter(x), (I,), **kw)
     assert torch.autograd.gradcheck(lambda x: lm.bspline_prefilter(x, adjoint=True), (I,), **kw)

@@ -15,6 +15,7 @@ import pytest
 import torch
 
 import edt_ref as ref
+from gpu_util import dev
 
 pytestmark = pytest.mark.gpu
 
@@ -24,10 +25,6 @@ SHAPES = ((5, 6, 7), (7, 9), (1, 9), (1, 5, 4), (6, 1, 3), (2, 2, 2), (8, 16, 32
 SPACING = (1.5, 0.7, 2.0)
 REL = 8 * 2.0 ** -24   # one rounding for s delta, one for the square, one per addition over three axes (and the
                        # spacing's own rounding to float32): every term is non-negative, so the errors only add
-
-
-def _dev(x):
-    return torch.from_numpy(np.array(x)).cuda()   # (a copy: the shared inputs are read-only)
 
 
 @functools.lru_cache(maxsize=None)
@@ -51,7 +48,7 @@ def test_unit_spacing_is_exact(sp):
 
     for kind in ref.KINDS:
         L = _labels(kind, sp)
-        Ld = _dev(L)
+        Ld = dev(L)
         if kind not in ("none", "all"):
             assert not np.array_equal(L[0], L[1])   # an item-stride error would show
         for where in ref.WHERES:
@@ -61,7 +58,7 @@ def test_unit_spacing_is_exact(sp):
             assert torch.equal(got.cpu(), torch.from_numpy(want)), (kind, where)
             got = lm.distance_transform(Ld, where, 1)
             assert torch.equal(got.cpu().view(torch.int32), torch.from_numpy(np.sqrt(want)).view(torch.int32)), (kind, where)
-    assert torch.equal(lm.distance_transform(_dev(_labels("dense", sp))).cpu(),   # the defaults: L != 0, unit spacing, the root
+    assert torch.equal(lm.distance_transform(dev(_labels("dense", sp))).cpu(),   # the defaults: L != 0, unit spacing, the root
                        torch.from_numpy(np.sqrt(_want_sq("dense", sp, "nonzero", 1.0).astype(np.float32))))
 
 
@@ -72,7 +69,7 @@ def test_anisotropic_spacing_is_within_the_derived_bound(sp):
     s = SPACING[-len(sp):]
     worst = 0.0
     for kind in ref.KINDS:
-        Ld = _dev(_labels(kind, sp))
+        Ld = dev(_labels(kind, sp))
         for where in ref.WHERES:
             want = _want_sq(kind, sp, where, s)
             got = lm.distance_transform(Ld, where, 1, s, squared=True).cpu().numpy().astype(np.float64)
@@ -86,7 +83,7 @@ def test_anisotropic_spacing_is_within_the_derived_bound(sp):
             assert np.array_equal(root.view(np.uint32), np.sqrt(got.astype(np.float32)).view(np.uint32)), (kind, where)
     print(f"{sp}: largest relative error {worst / 2.0 ** -24:.2f} * 2^-24 (bound 8)")
     # one spacing for all axes is that spacing on every axis
-    Ld = _dev(_labels("sparse", sp))
+    Ld = dev(_labels("sparse", sp))
     assert torch.equal(lm.distance_transform(Ld, spacing=0.7), lm.distance_transform(Ld, spacing=(0.7,) * len(sp)))
 
 
@@ -95,7 +92,7 @@ def test_dtypes_layout_determinism_and_limits():
 
     sp = (5, 6, 7)
     L = _labels("dense", sp)   # labels 0, 1, 2
-    Ld = _dev(L).requires_grad_(False)
+    Ld = dev(L).requires_grad_(False)
     want = lm.distance_transform(Ld, "equal", 1)
     assert want.dtype == torch.float32 and want.grad_fn is None and not want.requires_grad
     for dt in (torch.uint8, torch.int16, torch.int64):
@@ -125,7 +122,7 @@ def test_largest_extent():
         L[0, 0, 0, 0] = L[1, 0, -1, -1] = 1
         grid = np.indices(sp)
         want = np.stack([grid[0] ** 2 + grid[1] ** 2, (grid[0] - sp[0] + 1) ** 2 + (grid[1] - sp[1] + 1) ** 2])[:, None]
-        assert torch.equal(lm.distance_transform(_dev(L), squared=True).cpu(), torch.from_numpy(want.astype(np.float32)))
+        assert torch.equal(lm.distance_transform(dev(L), squared=True).cpu(), torch.from_numpy(want.astype(np.float32)))
 
 
 def test_signed_distance():
@@ -133,7 +130,7 @@ def test_signed_distance():
 
     sp = (9, 10, 11)
     L = _labels("blobs", sp)
-    Ld = _dev(L)
+    Ld = dev(L)
     for label, s in ((2, 1.0), (None, 1.0), (1, SPACING)):
         got = lm.signed_distance(Ld, label, s)
         assert got.dtype == torch.float32 and got.shape == L.shape
@@ -148,11 +145,11 @@ def test_signed_distance():
             assert torch.equal(got.cpu(), torch.from_numpy(out - ins))
     # the sign convention on a box: negative inside, positive outside, +-1 across a face
     B = np.concatenate([ref.box((9, 9), (3, 3), (6, 6), 4), ref.box((9, 9), (2, 3), (5, 6), 4)])
-    sd = lm.signed_distance(_dev(B), 4).cpu().numpy()
+    sd = lm.signed_distance(dev(B), 4).cpu().numpy()
     assert sd[0, 0, 4, 4] == -2 and sd[0, 0, 3, 4] == -1 and sd[0, 0, 2, 4] == 1 and sd[0, 0, 0, 0] == np.float32(np.sqrt(18.0))
     assert sd[1, 0, 3, 4] == -2 and sd[1, 0, 1, 4] == 1
     # an empty side is the other side's infinity
-    assert torch.all(lm.signed_distance(_dev(B), 7) == float("inf")) and torch.all(lm.signed_distance(_dev(B * 0 + 7), 7) == -float("inf"))
+    assert torch.all(lm.signed_distance(dev(B), 7) == float("inf")) and torch.all(lm.signed_distance(dev(B * 0 + 7), 7) == -float("inf"))
 
 
 def _check_surface(got, want, rel=1e-6):
@@ -179,12 +176,12 @@ def test_surface_distance_on_blobs(sp):
         want = ref.surface_distance(A, B, labels, s)
         assert np.isfinite(want["hausdorff"][:, 0]).all() and (want["assd"][:, 0] > 0).all()
         assert np.isnan(want["hd95"][:, 2]).all()
-        got = lm.surface_distance(_dev(A), _dev(B), labels, s)
+        got = lm.surface_distance(dev(A), dev(B), labels, s)
         _check_surface(got, want)
         for k in got:
             assert torch.all(got[k][:, 1] == 0), k
     # the selection mask is the kernel's own predicate
-    assert torch.equal(lm.surface_mask(_dev(A), 1).cpu(), torch.from_numpy(ref.surface(A == 1)))
+    assert torch.equal(lm.surface_mask(dev(A), 1).cpu(), torch.from_numpy(ref.surface(A == 1)))
 
 
 @pytest.mark.parametrize("d", [2, 3])
@@ -193,7 +190,7 @@ def test_surface_distance_on_the_closed_form_boxes(d):
 
     A, B, hausdorff, assd = ref.concentric_boxes(d)
     A2, B2 = np.concatenate([A, B]), np.concatenate([B, A])   # the second item the other way round: symmetric
-    got = lm.surface_distance(_dev(A2), _dev(B2), [1])
+    got = lm.surface_distance(dev(A2), dev(B2), [1])
     for n in range(2):
         assert abs(got["hausdorff"][n, 0].item() - hausdorff) <= 1e-6 * hausdorff
         assert abs(got["assd"][n, 0].item() - assd) <= 1e-6 * assd
@@ -204,7 +201,7 @@ def test_other_stream_gives_the_same_bits():
     import lagomorph_amd as lm
 
     sp = (33, 40, 41)
-    Ld = _dev(_labels("blobs", sp))
+    Ld = dev(_labels("blobs", sp))
     want = [lm.distance_transform(Ld, w, 1, SPACING) for w in ref.WHERES]
     torch.cuda.synchronize()
     side = torch.cuda.Stream()

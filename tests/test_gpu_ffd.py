@@ -22,20 +22,13 @@ import pytest
 import torch
 
 import ffd_ref as ref
+from gpu_util import dev, host
+from parity_rule import rtol, units
 
 pytestmark = pytest.mark.gpu
 
-RTOL = {np.dtype(np.float32): 1e-5, np.dtype(np.float64): 1e-12}
 both_dtypes = pytest.mark.parametrize("dtype", [np.float32, np.float64], ids=["f32", "f64"])
 cases = pytest.mark.parametrize("shape,spacing", ref.CASES, ids=str)
-
-
-def _dev(x):
-    return torch.from_numpy(np.ascontiguousarray(x)).cuda()
-
-
-def _host(x):
-    return x.detach().cpu().numpy()
 
 
 def _batches(d):
@@ -74,17 +67,17 @@ def test_forward(shape, spacing, dtype):
     worst = 0.0
     for N, C in _batches(len(shape)):
         c, want, bound = _forward_case(shape, spacing, np.dtype(dtype).name, N, C)
-        cd = _dev(c)
+        cd = dev(c)
         got = lm.ffd_expand(cd, shape, spacing)
         assert got.shape == (N, C) + tuple(shape) and got.dtype == cd.dtype and got.is_contiguous()
-        h = _host(got)
+        h = host(got)
         err = np.abs(h.astype(want.dtype) - want).astype(np.float64)
         ratio = ref.worst_ratio(err, bound)
         worst = max(worst, ratio)
         assert ratio <= 1.0, f"{shape} / {spacing} N {N} C {C}: {ratio:.3f} of the voxel bound"
-        assert err.max() <= RTOL[np.dtype(dtype)] * float(np.abs(want).max())
+        assert err.max() <= rtol(dtype) * float(np.abs(want).max())
         assert torch.equal(got, lm.ffd_expand(cd, shape, spacing))   # no atomics: the same bits
-        assert torch.equal(cd, _dev(c))                              # the input is left alone
+        assert torch.equal(cd, dev(c))                              # the input is left alone
     print(f"ffd_expand {shape} / {spacing} {np.dtype(dtype).name}: at most {worst:.3f} of the voxel bound")
 
 
@@ -98,19 +91,19 @@ def test_adjoint(shape, spacing, dtype):
     m = ref.grid_shape(shape, sp)
     for N, C in _batches(len(shape)):
         g, want, bound = _adjoint_case(shape, spacing, np.dtype(dtype).name, N, C)
-        gd = _dev(g)
+        gd = dev(g)
         got = lm.ffd_restrict(gd, spacing)
         assert got.shape == (N, C) + m and got.dtype == gd.dtype and got.is_contiguous()
-        h = _host(got).astype(np.float64)
+        h = host(got).astype(np.float64)
         err = np.abs(h - want)
         if dtype == np.float64:
-            assert err.max() <= 1e-12 * np.abs(want).max()
+            assert units(h, want, dtype, floor=0) <= 1.0
         else:
             ratio = ref.worst_ratio(err, bound)
             worst = max(worst, ratio)
             assert ratio <= 1.0, f"{shape} / {spacing} N {N} C {C}: {ratio:.3f} of the entry bound"
         assert torch.equal(got, lm.ffd_restrict(gd, spacing))   # no atomic on memory: the same bits
-        assert torch.equal(gd, _dev(g))
+        assert torch.equal(gd, dev(g))
         unused = 0
         for a, (n, s) in enumerate(zip(shape, sp)):   # entries that no voxel reaches with a weight: exactly 0
             if (n - 1) % s == 0:
@@ -125,8 +118,8 @@ def test_adjoint(shape, spacing, dtype):
 def test_adjoint_identity_float64(shape, spacing):
     import lagomorph_amd as lm
 
-    c = _dev(ref.field(2, 2, ref.grid_shape(shape, spacing), np.float64, seed=3))
-    g = _dev(ref.field(2, 2, shape, np.float64, seed=4))
+    c = dev(ref.field(2, 2, ref.grid_shape(shape, spacing), np.float64, seed=3))
+    g = dev(ref.field(2, 2, shape, np.float64, seed=4))
     lhs = float((lm.ffd_expand(c, shape, spacing) * g).sum())
     rhs = float((c * lm.ffd_restrict(g, spacing)).sum())
     scale = float((lm.ffd_expand(c.abs(), shape, spacing) * g.abs()).sum())
@@ -152,11 +145,11 @@ def test_unused_control_plane_is_exactly_zero_and_linear_lattices_expand_to_line
 def test_gradcheck_and_gradgradcheck(shape, spacing):
     import lagomorph_amd as lm
 
-    c = _dev(ref.field(1, 2, ref.grid_shape(shape, spacing), np.float64, seed=5)).requires_grad_(True)
+    c = dev(ref.field(1, 2, ref.grid_shape(shape, spacing), np.float64, seed=5)).requires_grad_(True)
     f = lambda x: lm.ffd_expand(x, shape, spacing)   # noqa: E731
     assert torch.autograd.gradcheck(f, (c,), eps=1e-6, atol=1e-8, rtol=1e-8, nondet_tol=0.0)
     assert torch.autograd.gradgradcheck(f, (c,), eps=1e-6, atol=1e-8, rtol=1e-8, nondet_tol=0.0)
-    g = _dev(ref.field(1, 2, shape, np.float64, seed=6)).requires_grad_(True)
+    g = dev(ref.field(1, 2, shape, np.float64, seed=6)).requires_grad_(True)
     assert torch.autograd.gradcheck(lambda x: lm.ffd_restrict(x, spacing), (g,), eps=1e-6, atol=1e-8, rtol=1e-8, nondet_tol=0.0)
 
 
@@ -168,7 +161,7 @@ def test_a_gradient_nobody_needs_runs_no_kernel(monkeypatch):
     real = ext.ffd_expand_adjoint
     monkeypatch.setattr(ext, "ffd_expand_adjoint", lambda *a: (calls.append(1), real(*a))[1])
     shape, spacing = (5, 6, 7), (2, 3, 4)
-    c = _dev(ref.field(1, 3, ref.grid_shape(shape, spacing), np.float32))
+    c = dev(ref.field(1, 3, ref.grid_shape(shape, spacing), np.float32))
     w = torch.ones((), device="cuda", requires_grad=True)
     out = lm.ffd_expand(c, shape, spacing)
     assert not out.requires_grad
@@ -189,9 +182,9 @@ def test_gradient_through_interp_is_the_restriction_of_d_u():
     import lagomorph_amd as lm
 
     shape, spacing = (12, 10, 14), (4, 3, 5)
-    I = _dev(ref.field(2, 1, shape, np.float32, seed=8))
-    go = _dev(ref.field(2, 1, shape, np.float32, seed=9))
-    c = (0.7 * _dev(ref.field(2, 3, ref.grid_shape(shape, spacing), np.float32, seed=10))).requires_grad_(True)
+    I = dev(ref.field(2, 1, shape, np.float32, seed=8))
+    go = dev(ref.field(2, 1, shape, np.float32, seed=9))
+    c = (0.7 * dev(ref.field(2, 3, ref.grid_shape(shape, spacing), np.float32, seed=10))).requires_grad_(True)
     (lm.interp(I, lm.ffd_expand(c, shape, spacing)) * go).sum().backward()
     u = lm.ffd_expand(c.detach(), shape, spacing).requires_grad_(True)
     (lm.interp(I, u) * go).sum().backward()
@@ -229,8 +222,8 @@ def test_non_default_stream_gives_the_same_bits(dtype):
     import lagomorph_amd as lm
 
     for shape, spacing in (((70, 37, 75), (5, 3, 7)), ((97, 70), (32, 7))):
-        c = _dev(ref.field(2, 2, ref.grid_shape(shape, spacing), dtype))
-        g = _dev(ref.field(2, 2, shape, dtype, seed=7))
+        c = dev(ref.field(2, 2, ref.grid_shape(shape, spacing), dtype))
+        g = dev(ref.field(2, 2, shape, dtype, seed=7))
         want_f, want_a = lm.ffd_expand(c, shape, spacing), lm.ffd_restrict(g, spacing)
         torch.cuda.synchronize()
         stream = torch.cuda.Stream()

@@ -9,17 +9,14 @@ import pytest
 import torch
 
 import gauss_ref
+from gpu_util import DTYPES, NPDT, SHAPES2, SHAPES3, dev, host, units_of
+from parity_rule import rtol
 
 pytestmark = pytest.mark.gpu
 
-DTYPES = [torch.float32, torch.float64]
-RTOL = {torch.float32: 1e-5, torch.float64: 1e-12}
-NPDT = {torch.float32: np.float32, torch.float64: np.float64}
 MODES = ["wrap", "zero"]
-# the lists of tests/test_gpu_parity.py, then shapes around the kernels' tile edges (64 positions of a strided axis per
+# after the lists of tests/gpu_util.py: shapes around the kernels' tile edges (64 positions of a strided axis per
 # workgroup, 4 outputs per lane, rows of more than 128 voxels) and the smallest grid
-SHAPES3 = [(5, 6, 7), (8, 8, 8), (3, 4, 1), (2, 2, 2), (9, 5, 70), (6, 5, 16), (3, 4, 128)]
-SHAPES2 = [(7, 9), (16, 16), (2, 2), (5, 1), (3, 130)]
 EDGES = [(65, 3, 5), (4, 66, 3), (3, 4, 130), (33, 33, 33), (1, 1, 1)]
 
 
@@ -57,19 +54,6 @@ def reference(sp, dtype, sigma, mode, seed=0, nn=3, nc=3):
         r.setflags(write=False)
         _REFS[key] = r
     return _REFS[key]
-
-
-def dev(a):
-    return torch.from_numpy(np.array(a, order="C")).cuda()
-
-
-def host(t):
-    return t.detach().cpu().numpy()
-
-
-def units_of(got, want, dtype, scale=None):
-    """max |got - want| in units of RTOL x max|want| (or x scale): gauss_ref.units, which tests/fuzz_ops_cases.py shares."""
-    return gauss_ref.units(host(got), want, NPDT[dtype], scale)
 
 
 def same_values(a, b):
@@ -281,7 +265,7 @@ def test_operator_is_self_adjoint(lm, dtype, sp):
     """<G x, y> against <x, G y>, both sums in float64 on the host.  Each side carries at most RTOL x |x| |y| of error
     (|G x - ref| <= RTOL max|ref| per element is far inside RTOL |x| in norm for these fields), hence 2 RTOL |x| |y|."""
     x, y = field(sp, dtype, nn=2, nc=2), field(sp, dtype, seed=5, nn=2, nc=2)
-    bound = 2 * RTOL[dtype] * np.linalg.norm(x.astype(np.float64)) * np.linalg.norm(y.astype(np.float64))
+    bound = 2 * rtol(dtype) * np.linalg.norm(x.astype(np.float64)) * np.linalg.norm(y.astype(np.float64))
     for sigma in sigma_sets(len(sp)):
         for mode in MODES:
             gx = host(lm.gaussian_smooth(dev(x), sigma, mode=mode)).astype(np.float64)

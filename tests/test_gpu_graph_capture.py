@@ -15,15 +15,9 @@ import numpy as np
 import pytest
 import torch
 
+from gpu_util import smooth_field
+
 pytestmark = pytest.mark.gpu
-
-
-def _smooth(shape, sigma, seed, amp):
-    import bench
-
-    g = torch.Generator(device="cuda").manual_seed(seed)
-    x = bench.gaussian_blur(torch.randn(shape, device="cuda", generator=g), sigma)
-    return (x * (amp / x.abs().max())).contiguous()
 
 
 def _capture(fn, warm=3):
@@ -48,7 +42,7 @@ def test_captured_expmap_replays_same_bits(sp, B, steps):
 
     d = len(sp)
     met = lm.FluidMetric([0.1, 0.0, 0.01])
-    m = _smooth((B, d) + sp, 3.0, 1, 1.0)
+    m = smooth_field((B, d) + sp, 3.0, 1, 1.0)
     with torch.no_grad():
         m *= 2.5 / met.sharp(m).abs().max()
         assert lddmm.EXPMAP_STREAMS == 2   # the default path: two sub-batches on side streams, inside the capture too
@@ -59,7 +53,7 @@ def test_captured_expmap_replays_same_bits(sp, B, steps):
             torch.cuda.synchronize()
             assert torch.equal(out, ref)
         # the graph reads its input tensor at replay time: new momenta, new displacement
-        m2 = _smooth((B, d) + sp, 2.0, 2, 1.0)
+        m2 = smooth_field((B, d) + sp, 2.0, 2, 1.0)
         m2 *= 1.5 / met.sharp(m2).abs().max()
         ref2 = lm.expmap(met, m2, num_steps=steps)
         m.copy_(m2)
@@ -75,9 +69,9 @@ def test_captured_lddmm_step_replays(sp):
 
     d, B = len(sp), 4
     met = lm.FluidMetric([0.1, 0.0, 0.01])
-    I0 = _smooth((1, 1) + sp, 2.0, 3, 1.0)
-    img = (I0 + 0.2 * _smooth((B, 1) + sp, 2.0, 4, 1.0)).contiguous()
-    m0 = _smooth((B, d) + sp, 3.0, 5, 1.0)
+    I0 = smooth_field((1, 1) + sp, 2.0, 3, 1.0)
+    img = (I0 + 0.2 * smooth_field((B, 1) + sp, 2.0, 4, 1.0)).contiguous()
+    m0 = smooth_field((B, d) + sp, 3.0, 5, 1.0)
     with torch.no_grad():
         m0 *= 1.5 / met.sharp(m0).abs().max()
     V = float(np.prod(sp))
@@ -129,7 +123,7 @@ def test_first_use_inside_a_capture_fails_loudly():
     ext.fluid_cache_clear() if hasattr(ext, "fluid_cache_clear") else None
     sp = (40, 24, 48)   # a tuned-pass shape (powers of two times 3 / 5) no other test of this file uses
     met = lm.FluidMetric([0.13, 0.0, 0.017])   # parameters of its own: no table from another test matches
-    m = _smooth((2, 3) + sp, 2.0, 9, 1.0)
+    m = smooth_field((2, 3) + sp, 2.0, 9, 1.0)
     side = torch.cuda.Stream()
     side.wait_stream(torch.cuda.current_stream())
     torch.cuda.synchronize()

@@ -10,15 +10,10 @@ import pytest
 import torch
 
 import invert_ref
+from gpu_util import DTYPES, NPDT, SHAPES2, SHAPES3, assert_bits, dev, host, rnd, smooth_field, units_of
+from parity_rule import rtol
 
 pytestmark = pytest.mark.gpu
-
-DTYPES = [torch.float32, torch.float64]
-RTOL = {torch.float32: 1e-5, torch.float64: 1e-12}
-# the lists of tests/test_gpu_parity.py
-SHAPES3 = [(5, 6, 7), (8, 8, 8), (3, 4, 1), (2, 2, 2), (9, 5, 70), (6, 5, 16), (3, 4, 128)]
-SHAPES2 = [(7, 9), (16, 16), (2, 2), (5, 1), (3, 130)]
-NPDT = {torch.float32: np.float32, torch.float64: np.float64}
 
 
 @pytest.fixture(scope="module")
@@ -30,49 +25,12 @@ def lm():
     lagomorph_amd.set_debug_mode(False)
 
 
-def rnd(rng, shape, dtype, scale=1.0):
-    return (scale * rng.standard_normal(shape)).astype(NPDT[dtype])
-
-
-def dev(a):
-    return torch.from_numpy(np.array(a, order="C")).cuda()   # (a copy: the shared reference arrays are read-only)
-
-
-def host(t):
-    return t.detach().cpu().numpy()
-
-
-def assert_bits(got, want, what):
-    got, want = host(got), host(want) if isinstance(want, torch.Tensor) else np.asarray(want)
-    assert got.shape == want.shape and got.dtype == want.dtype, f"{what}: {got.shape} {got.dtype} vs {want.shape} {want.dtype}"
-    if not np.array_equal(got, want):
-        d = np.abs(got.astype(np.float64) - want.astype(np.float64))
-        raise AssertionError(f"{what}: not bit-identical, max abs diff {d.max():.3e} at {np.unravel_index(d.argmax(), d.shape)}")
-
-
-def units_of(got, want, dtype, scale=None):
-    """max |got - want| in units of RTOL x scale (scale: max|want| unless given)."""
-    got, want = host(got).astype(np.float64), np.asarray(want).astype(np.float64)
-    assert got.shape == want.shape, f"shape {got.shape} vs {want.shape}"
-    ref = np.abs(want).max() if scale is None else scale
-    err = np.abs(got - want).max() if got.size else 0.0
-    return err / (RTOL[dtype] * max(ref, 1e-300))
-
-
 def loop(ext, u, iters):
     """The unfused iteration over the existing operators."""
     v = -u
     for _ in range(iters):
         v = -ext.interp_forward(u, v, 1.0)
     return v
-
-
-def _smooth(shape, sigma, seed, amp):
-    import bench
-
-    g = torch.Generator(device="cuda").manual_seed(seed)
-    x = bench.gaussian_blur(torch.randn(shape, device="cuda", generator=g), sigma)
-    return (x * (amp / x.abs().max())).contiguous()
 
 
 # ---- 1. forward bits against the unfused loop
@@ -97,7 +55,7 @@ def test_forward_bits_production_geometry(lm):
     """2 x 3 x 128^3 float32, 5 steps, a smooth field of amplitude 2: the loop's interp_forward runs its vectorised
     production kernels here."""
     ext = lm.lagomorph_ext
-    u = _smooth((2, 3, 128, 128, 128), 8.0, 228, 2.0)
+    u = smooth_field((2, 3, 128, 128, 128), 8.0, 228, 2.0)
     got = ext.invert_displacement_forward(u, 5)
     want = loop(ext, u, 5)
     assert torch.equal(got, want), f"not bit-identical: max abs diff {float((got - want).abs().max()):.3e}"
@@ -142,7 +100,7 @@ def test_it_is_an_inverse(lm, oracle_fields, dtype, sp):
     """compose(v, u) = (id + u) o (id + v) - id vanishes to 2 RTOL max|u| at 60 steps -- and does not at 1 step, so
     the check can fail."""
     u = dev(oracle_fields(dtype, sp)[0])
-    bound = 2 * RTOL[dtype] * float(u.abs().max())
+    bound = 2 * rtol(dtype) * float(u.abs().max())
     res60 = float(lm.compose(lm.invert_displacement(u, 60), u).abs().max())
     res1 = float(lm.compose(lm.invert_displacement(u, 1), u).abs().max())
     print(f"{sp} {dtype}: residual at 60 steps {res60 / bound:.3e}, at 1 step {res1 / bound:.3e} of the bound")
@@ -266,7 +224,7 @@ def test_on_a_field_the_library_produced(lm):
     """h = expmap(metric, m0) in 5 steps at 1 x 3 x 32^3: the default 20 steps leave a smaller residual than 1 step."""
     sp = (32, 32, 32)
     met = lm.FluidMetric([0.1, 0.0, 0.01])
-    m = _smooth((1, 3) + sp, 3.0, 31, 1.0)
+    m = smooth_field((1, 3) + sp, 3.0, 31, 1.0)
     with torch.no_grad():
         m *= 0.5 / met.sharp(m).abs().max()   # initial velocity of at most half a voxel
         h = lm.expmap(met, m, num_steps=5)

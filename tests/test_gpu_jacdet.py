@@ -1,22 +1,20 @@
 """GPU: jacobian_determinant (csrc/diff.hip: jacdet_fwd_kernel / jacdet_bwd_kernel) against the test-side reference
 built from the CPU oracle (tests/jacdet_ref.py).  Forward bit for bit; backward within the project's tolerance
 (RTOL x max|reference|, no multipliers, as tests/test_gpu_parity.py) and bit-identical from call to call."""
+import functools
 import os
 
 import numpy as np
 import pytest
 import torch
 
+import gpu_util
 import jacdet_ref
+from gpu_util import DTYPES, SHAPES2, SHAPES3, assert_bits, dev, host, rnd, smooth_field
 from oracle import lago_oracle as orc
 
 pytestmark = pytest.mark.gpu
-
-DTYPES = [torch.float32, torch.float64]
-RTOL = {torch.float32: 1e-5, torch.float64: 1e-12}
-# the lists of tests/test_gpu_parity.py
-SHAPES3 = [(5, 6, 7), (8, 8, 8), (3, 4, 1), (2, 2, 2), (9, 5, 70), (6, 5, 16), (3, 4, 128)]
-SHAPES2 = [(7, 9), (16, 16), (2, 2), (5, 1), (3, 130)]
+assert_close = functools.partial(gpu_util.assert_close, record=False, show=True)   # prints the units, stays out of LAGO_TOL_REPORT
 
 
 @pytest.fixture(scope="module")
@@ -26,36 +24,6 @@ def lm():
     lagomorph_amd.set_debug_mode(True)
     yield lagomorph_amd
     lagomorph_amd.set_debug_mode(False)
-
-
-def rnd(rng, shape, dtype, scale=1.0):
-    return (scale * rng.standard_normal(shape)).astype(np.float32 if dtype == torch.float32 else np.float64)
-
-
-def dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
-
-
-def host(t):
-    return t.detach().cpu().numpy()
-
-
-def assert_bits(got, want, what):
-    got, want = host(got), np.asarray(want)
-    assert got.shape == want.shape and got.dtype == want.dtype, f"{what}: {got.shape} {got.dtype} vs {want.shape} {want.dtype}"
-    if not np.array_equal(got, want):
-        d = np.abs(got.astype(np.float64) - want.astype(np.float64))
-        raise AssertionError(f"{what}: not bit-identical, max abs diff {d.max():.3e} at {np.unravel_index(d.argmax(), d.shape)}")
-
-
-def assert_close(got, want, dtype, what):
-    got, want = host(got).astype(np.float64), np.asarray(want).astype(np.float64)
-    assert got.shape == want.shape, f"{what}: shape {got.shape} vs {want.shape}"
-    ref = np.abs(want).max()
-    err = np.abs(got - want).max() if got.size else 0.0
-    units = err / (RTOL[dtype] * max(ref, 1e-30))
-    print(f"{what}: {units:.4f} of {RTOL[dtype]:.0e} x max|ref|")
-    assert units <= 1.0, f"{what}: max err {err:.3e} = {units:.2f} x {RTOL[dtype]:.0e} x scale {ref:.3e} (allowed 1)"
 
 
 @pytest.mark.parametrize("dtype", DTYPES)
@@ -76,14 +44,6 @@ def test_forward_bits_backward_tolerance(lm, dtype, sp):
                 assert torch.equal(d1, d2), "backward differs between two calls: " + what
 
 
-def _smooth(shape, sigma, seed, amp):
-    import bench
-
-    g = torch.Generator(device="cuda").manual_seed(seed)
-    x = bench.gaussian_blur(torch.randn(shape, device="cuda", generator=g), sigma)
-    return (x * (amp / x.abs().max())).contiguous()
-
-
 def _oracle_threads():
     return min(os.cpu_count() or 1, 64)
 
@@ -92,7 +52,7 @@ def _oracle_threads():
 def test_production_geometry(lm, N, S):
     """8 x 3 x 128^3 and 2 x 3 x 160^3 float32, a smooth displacement of about 3 voxels amplitude."""
     ext = lm.lagomorph_ext
-    u = _smooth((N, 3, S, S, S), 8.0, 100 + S, 3.0)
+    u = smooth_field((N, 3, S, S, S), 8.0, 100 + S, 3.0)
     g = torch.Generator(device="cuda").manual_seed(S)
     go = torch.randn((N, 1, S, S, S), device="cuda", generator=g)
     out = ext.jacobian_determinant_forward(u, True)
@@ -189,8 +149,8 @@ def test_graph_capture(lm, shape):
     ext = lm.lagomorph_ext
     lm.set_debug_mode(False)   # debug mode synchronises after every launch: not capturable
     try:
-        u = _smooth(shape, 2.0, 21, 2.0)
-        go = _smooth((shape[0], 1) + shape[2:], 1.0, 22, 1.0)
+        u = smooth_field(shape, 2.0, 21, 2.0)
+        go = smooth_field((shape[0], 1) + shape[2:], 1.0, 22, 1.0)
 
         def fn():
             return ext.jacobian_determinant_forward(u, True), ext.jacobian_determinant_backward(go, u, True)
@@ -210,7 +170,7 @@ def test_graph_capture(lm, shape):
             graph.replay()
             torch.cuda.synchronize()
             assert torch.equal(out[0], ref[0]) and torch.equal(out[1], ref[1])
-        u2 = _smooth(shape, 3.0, 23, 1.0)
+        u2 = smooth_field(shape, 3.0, 23, 1.0)
         ref2 = (ext.jacobian_determinant_forward(u2, True), ext.jacobian_determinant_backward(go, u2, True))
         u.copy_(u2)
         graph.replay()
@@ -226,7 +186,7 @@ def test_on_a_field_the_library_produced(lm):
     reference finds no folded voxel, and then the kernel finds none either."""
     sp = (24, 20, 36)
     met = lm.FluidMetric([0.1, 0.0, 0.01])
-    m = _smooth((2, 3) + sp, 3.0, 31, 1.0)
+    m = smooth_field((2, 3) + sp, 3.0, 31, 1.0)
     with torch.no_grad():
         m *= 0.5 / met.sharp(m).abs().max()   # initial velocity of at most half a voxel
         h = lm.expmap(met, m, num_steps=10)

@@ -10,6 +10,7 @@ import pytest
 import torch
 
 import labels_ref as ref
+from gpu_util import dev
 
 pytestmark = pytest.mark.gpu
 
@@ -17,10 +18,6 @@ N = 2
 WARP_SHAPES = ((5, 6, 7), (7, 9), (8, 16, 32), (1, 5, 4), (6, 1, 3), (2, 2, 2), (1, 9))
 OVERLAP_SHAPES = ((5, 6, 7), (33, 40, 41), (7, 9))
 KS = (1, 2, 5, 200, 4096)
-
-
-def _dev(x):
-    return torch.from_numpy(np.ascontiguousarray(x)).cuda()
 
 
 @pytest.mark.parametrize("dtype", [np.float32, np.float64], ids=["f32", "f64"])
@@ -33,10 +30,10 @@ def test_warp_labels_equals_the_reference(sp, dtype):
     calls = 0
     before = ext.path_launches("vector_gather")
     for lk, dk, dt, L, u in ref.warp_cases(N, sp, dtype):
-        ud = _dev(u)
+        ud = dev(u)
         for bc in (False, True):
             Lh = L[:1] if bc else L
-            Ld = _dev(Lh)
+            Ld = dev(Lh)
             for mode in ref.MODES:
                 got = lm.warp_labels(Ld, ud, dt, mode)
                 calls += 1
@@ -52,21 +49,21 @@ def test_warp_labels_dtypes_defaults_and_no_graph():
     sp = (5, 6, 7)
     L = ref.labels("random5", N, sp)
     u = ref.displacement("random", N, sp, np.float32)
-    ud = _dev(u).requires_grad_(True)
-    want = lm.warp_labels(_dev(L), ud)
+    ud = dev(u).requires_grad_(True)
+    want = lm.warp_labels(dev(L), ud)
     assert torch.equal(want.cpu(), torch.from_numpy(ref.warp(L, u, 1.0, "vote")))   # the defaults: dt = 1, vote
     assert not want.requires_grad and want.grad_fn is None and want.dtype == torch.int32
     for dt in (torch.uint8, torch.int16, torch.int64):
-        got = lm.warp_labels(_dev(L).to(dt), ud, mode="vote")
+        got = lm.warp_labels(dev(L).to(dt), ud, mode="vote")
         assert got.dtype == dt and torch.equal(got.to(torch.int32), want) and not got.requires_grad
     # label values of the whole int32 range survive the int64 round trip
     Lx = ref.labels("extreme", N, sp)
-    got = lm.warp_labels(_dev(Lx).to(torch.int64), ud)
+    got = lm.warp_labels(dev(Lx).to(torch.int64), ud)
     assert got.dtype == torch.int64 and torch.equal(got.cpu(), torch.from_numpy(ref.warp(Lx, u, 1.0, "vote")).to(torch.int64))
     # determinism
-    assert torch.equal(lm.warp_labels(_dev(L), ud), want)
+    assert torch.equal(lm.warp_labels(dev(L), ud), want)
     with pytest.raises(RuntimeError, match="contiguous"):
-        lm.warp_labels(_dev(L).transpose(2, 3), _dev(u).transpose(2, 3))
+        lm.warp_labels(dev(L).transpose(2, 3), dev(u).transpose(2, 3))
 
 
 def _overlap_inputs(sp, K):
@@ -98,8 +95,8 @@ def test_label_overlap_equals_bincount(sp, K):
     if sp == (33, 40, 41):
         assert chunks >= 2          # 54 120 voxels: a row is shared by several workgroups
     for name, A, B in _overlap_inputs(sp, K):
-        Ad = _dev(A)
-        Bd = Ad if name == "same" else _dev(B)
+        Ad = dev(A)
+        Bd = Ad if name == "same" else dev(B)
         got = lm.label_overlap(Ad, Bd, K)
         assert got.dtype == torch.int64 and got.shape == (N, K, 3)
         want = ref.overlap(A, B, K)
@@ -165,7 +162,7 @@ def test_two_ragged_chunks_a_row_equal_one_chunk_a_row(sp, K):
     A = rng.integers(-3, K + 3, (rows, 1) + sp).astype(np.int32)
     B = np.where(rng.random(A.shape) < 0.5, A, rng.integers(-3, K + 3, A.shape)).astype(np.int32)
     A.reshape(-1)[:3] = (-2 ** 31, 2 ** 31 - 1, K)
-    Ad, Bd = _dev(A), _dev(B)
+    Ad, Bd = dev(A), dev(B)
     got = lm.label_overlap(Ad, Bd, K)
     assert torch.equal(got.cpu(), torch.from_numpy(ref.overlap(A, B, K)))
     assert torch.equal(_overlap_with_scratch(Ad, Bd, K, 1), got)
@@ -179,7 +176,7 @@ def test_label_overlap_of_the_smallest_rows(sp):
 
     K, rng = 3, np.random.default_rng([3, *sp])
     A, B = (rng.integers(-1, K + 1, (N, 1) + sp).astype(np.int32) for _ in range(2))
-    assert torch.equal(lm.label_overlap(_dev(A), _dev(B), K).cpu(), torch.from_numpy(ref.overlap(A, B, K)))
+    assert torch.equal(lm.label_overlap(dev(A), dev(B), K).cpu(), torch.from_numpy(ref.overlap(A, B, K)))
 
 
 def test_label_overlap_dtypes():
@@ -189,7 +186,7 @@ def test_label_overlap_dtypes():
     A, B = ref.labels("random5", N, sp), ref.labels("blobs", N, sp)
     want = torch.from_numpy(ref.overlap(A, B, K))
     for dt in (torch.uint8, torch.int16, torch.int32, torch.int64):
-        assert torch.equal(lm.label_overlap(_dev(A).to(dt), _dev(B).to(dt), K).cpu(), want)
+        assert torch.equal(lm.label_overlap(dev(A).to(dt), dev(B).to(dt), K).cpu(), want)
 
 
 def test_warp_back_reproduces_the_labels_and_dice_is_one():
@@ -205,7 +202,7 @@ def test_warp_back_reproduces_the_labels_and_dice_is_one():
     inside = torch.tensor([[k > 0 and bool((L[n] == k).any()) for k in range(K)] for n in range(N)])   # (N, K): the blobs
     assert int(inside.sum()) >= 6
     u = np.broadcast_to(np.array(s, dtype=np.float32).reshape(1, 3, 1, 1, 1), (N, 3) + sp)
-    Ld, ud = _dev(L), _dev(u)
+    Ld, ud = dev(L), dev(u)
     for mode in ref.MODES:
         moved = lm.warp_labels(Ld, ud, 1.0, mode)
         assert not torch.equal(moved, Ld)
@@ -222,8 +219,8 @@ def test_both_operators_capture_in_a_graph():
     import lagomorph_amd as lm
 
     sp, K = (8, 16, 32), 6
-    L = _dev(ref.labels("blobs", N, sp))
-    u = _dev(ref.displacement("random", N, sp, np.float32))
+    L = dev(ref.labels("blobs", N, sp))
+    u = dev(ref.displacement("random", N, sp, np.float32))
 
     def fn():
         w = lm.warp_labels(L, u)
@@ -244,7 +241,7 @@ def test_both_operators_capture_in_a_graph():
         graph.replay()
         torch.cuda.synchronize()
         assert torch.equal(out[0], want[0]) and torch.equal(out[1], want[1])
-    u.copy_(_dev(ref.displacement("half", N, sp, np.float32)))
+    u.copy_(dev(ref.displacement("half", N, sp, np.float32)))
     want2 = [x.clone() for x in fn()]
     graph.replay()
     torch.cuda.synchronize()

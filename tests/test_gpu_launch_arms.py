@@ -12,16 +12,19 @@ kernel family really ran.  The shapes follow from make_shear / make_tiles / slab
  * slab-unrolled gathers: nz >= 2, 256 / nz + 1 < ny, at least 2048 voxels; LDS window: at least 32768 voxels.
 """
 import contextlib
+import functools
 import itertools
 
 import numpy as np
 import pytest
 import torch
 
+import gpu_util
+from gpu_util import assert_close, dev, displacement, rnd
 from oracle import lago_oracle as orc
-from test_gpu_parity import _disp, assert_bits, assert_close, dev, rnd
 
 pytestmark = pytest.mark.gpu
+assert_bits = functools.partial(gpu_util.assert_bits, check_dtype=False)   # these sites compare shape and bits, as they always did
 
 F32, F64 = torch.float32, torch.float64
 BOOLS = (False, True)
@@ -62,7 +65,7 @@ def _splat_sweep(ext, sp, dtype, want_path, needs=((True, True), (True, False)),
     """interp_backward over bc x (need_I, need_u) x dt x nc; want_path(nc, need_I, need_u) names the counter."""
     nn = 2
     rng = np.random.default_rng(hash(sp + (dtype == F64,)) % 2**31)
-    u = _disp(rng, nn, sp, dtype)
+    u = displacement(rng, nn, sp, dtype)
     for nc, bc in itertools.product(ncs, BOOLS):
         I = rnd(rng, ((1 if bc else nn), nc) + sp, dtype)
         go = rnd(rng, (nn, nc) + sp, dtype)
@@ -114,7 +117,7 @@ def test_global_atomics_splat_arms(ext, sp, dtype):
         _splat_sweep(ext, sp, dtype, lambda nc, need_I, need_u: "splat_global",
                      needs=((True, True), (True, False), (False, True)))
         rng = np.random.default_rng(3)
-        go, u = rnd(rng, (2, 1) + sp, dtype), _disp(rng, 2, sp, dtype)
+        go, u = rnd(rng, (2, 1) + sp, dtype), displacement(rng, 2, sp, dtype)
         (dI, du), took = _took(ext, lambda: ext.interp_backward(dev(go), dev(go), dev(u), 1.0, False, False))
         assert took == {} and not dI.any() and not du.any()
 
@@ -130,7 +133,7 @@ def test_interp_forward_arms(ext, sp, nc, path):
     """unit x bc of the window and the slab-unrolled kernels, dim x bc of the plain one."""
     nn = 2
     rng = np.random.default_rng(hash(sp) % 2**31)
-    u = rnd(rng, (nn, len(sp)) + sp, F32, 0.5) if path else _disp(rng, nn, sp, F32)
+    u = rnd(rng, (nn, len(sp)) + sp, F32, 0.5) if path else displacement(rng, nn, sp, F32)
     for bc, dt in itertools.product(BOOLS, (1.0, -0.3)):
         I = rnd(rng, ((1 if bc else nn), nc) + sp, F32)
         out, took = _took(ext, lambda: ext.interp_forward(dev(I), dev(u), dt))

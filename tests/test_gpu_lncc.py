@@ -10,11 +10,11 @@ import pytest
 import torch
 
 import lncc_ref
+from gpu_util import DTYPES, NPDT, dev, host, units_of
+from parity_rule import rtol
 
 pytestmark = pytest.mark.gpu
 
-DTYPES = [torch.float32, torch.float64]
-NPDT = {torch.float32: np.float32, torch.float64: np.float64}
 MODES = lncc_ref.MODES
 
 
@@ -25,19 +25,6 @@ def lm():
     lagomorph_amd.set_debug_mode(True)
     yield lagomorph_amd
     lagomorph_amd.set_debug_mode(False)
-
-
-def dev(a, dtype=None):
-    t = torch.from_numpy(np.array(a, order="C"))
-    return (t if dtype is None else t.to(dtype)).cuda()
-
-
-def host(t):
-    return t.detach().cpu().numpy()
-
-
-def units_of(got, want, dtype):
-    return lncc_ref.units(host(got), want, NPDT[dtype])
 
 
 def case(sp, kind, dtype, grad=True):
@@ -349,7 +336,7 @@ def test_loss_reductions(lm, dtype):
     assert torch.equal(lm.lncc_loss(I, J, sigma, mode="zero"), none.mean())
     assert torch.equal(lm.LNCCSimilarity(sigma, mode="zero")(I, J), none.sum())
     ref = lncc_ref.reference(sp, "corr", sigma, "zero")[0]
-    assert abs(float(lm.lncc_loss(I, J, sigma, mode="zero")) - (1.0 - ref.mean())) <= lncc_ref.RTOL[NPDT[dtype]] * 10
+    assert abs(float(lm.lncc_loss(I, J, sigma, mode="zero")) - (1.0 - ref.mean())) <= rtol(dtype) * 10
     # the gradient of the mean: -dI / numel with g = 1
     Ig = I.clone().requires_grad_(True)
     lm.lncc_loss(Ig, J, sigma, mode="zero").backward()

@@ -11,11 +11,10 @@ import pytest
 import torch
 
 import mi_ref
+from gpu_util import DTYPES, NPDT, dev, host, units_of
 
 pytestmark = pytest.mark.gpu
 
-DTYPES = [torch.float32, torch.float64]
-NPDT = {torch.float32: np.float32, torch.float64: np.float64}
 
 
 @pytest.fixture(scope="module")
@@ -25,19 +24,6 @@ def lm():
     lagomorph_amd.set_debug_mode(True)
     yield lagomorph_amd
     lagomorph_amd.set_debug_mode(False)
-
-
-def dev(a, dtype=None):
-    t = torch.from_numpy(np.array(a, order="C"))
-    return (t if dtype is None else t.to(dtype)).cuda()
-
-
-def host(t):
-    return t.detach().cpu().numpy()
-
-
-def units_of(got, want, dtype):
-    return mi_ref.units(host(got), want, NPDT[dtype])
 
 
 def case(lead, sp, kind, dtype, grad=True):

@@ -3,24 +3,24 @@ seeded inputs.  Bit-exact wherever no atomic is involved (the library is built w
 -ffp-contract=off and follows the reference's expression order); tolerance-based for
 scatter-add results, whose summation order is unspecified in the reference too.
 """
+import functools
 import json
 import os
-import re
 
 import numpy as np
 import pytest
 import torch
 
+import gpu_util
 import kat
+from gpu_util import DTYPES, OBSERVED, SHAPES2, SHAPES3, assert_close, dev, displacement, host, rnd
 from oracle import lago_oracle as orc
 
 pytestmark = pytest.mark.gpu
-
-DTYPES = [torch.float32, torch.float64]
-# fp32 tolerance from BASELINE.json north_star: <=1e-5 relative for interp/metric outputs.  Every tolerance-based
-# comparison of this file uses exactly this bound (no multipliers): the largest error observed on MI355X is 0.58 of it
-# (affine d_I, float32; profiles/r02_tolerances.json lists every comparison), 0.016 of the float64 bound.
-RTOL = {torch.float32: 1e-5, torch.float64: 1e-12}
+assert_bits = functools.partial(gpu_util.assert_bits, check_dtype=False)   # these sites compare shape and bits, as they always did
+# Every tolerance-based comparison of this file uses exactly parity_rule.RTOL (fp32: BASELINE.json north_star, <=1e-5
+# relative for interp/metric outputs; no multipliers): the largest error observed on MI355X is 0.58 of it (affine d_I,
+# float32; profiles/r02_tolerances.json lists every comparison), 0.016 of the float64 bound.
 
 
 @pytest.fixture(scope="module")
@@ -34,65 +34,13 @@ def ext():
         json.dump(dict(sorted(OBSERVED.items())), open(out, "w"), indent=1)
 
 
-def rnd(rng, shape, dtype, scale=1.0):
-    a = (scale * rng.standard_normal(shape)).astype(np.float32 if dtype == torch.float32 else np.float64)
-    return a
-
-
-def dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
-
-
-def host(t):
-    return t.detach().cpu().numpy()
-
-
-def assert_bits(got, want, what):
-    got, want = host(got), np.asarray(want)
-    assert got.shape == want.shape, f"{what}: shape {got.shape} vs {want.shape}"
-    if not np.array_equal(got, want):
-        d = np.abs(got.astype(np.float64) - want.astype(np.float64))
-        raise AssertionError(f"{what}: not bit-identical, max abs diff {d.max():.3e} at {np.unravel_index(d.argmax(), d.shape)}")
-
-
-OBSERVED = {}  # what -> largest observed error in units of RTOL * scale (tools/tolerance_report.py prints it)
-
-
-def assert_close(got, want, dtype, what, scale=None):
-    """|got - want| <= RTOL[dtype] * scale, scale = max |want| unless given.  RTOL is north_star's 1e-5 for float32
-    (1e-12 for float64), without multipliers; the observed errors are in DESIGN.md section 3."""
-    got, want = host(got).astype(np.float64), np.asarray(want).astype(np.float64)
-    assert got.shape == want.shape, f"{what}: shape {got.shape} vs {want.shape}"
-    ref = np.abs(want).max() if scale is None else scale
-    err = np.abs(got - want).max() if got.size else 0.0
-    units = err / (RTOL[dtype] * max(ref, 1e-30))
-    key = re.sub(r"[\(\[].*$", "", what).strip() + (" f32" if dtype == torch.float32 else " f64")
-    OBSERVED[key] = max(OBSERVED.get(key, 0.0), units)
-    assert units <= 1.0, f"{what}: max err {err:.3e} = {units:.2f} x {RTOL[dtype]:.0e} x scale {ref:.3e} (allowed 1)"
-
-
-SHAPES3 = [(5, 6, 7), (8, 8, 8), (3, 4, 1), (2, 2, 2), (9, 5, 70), (6, 5, 16), (3, 4, 128)]
-SHAPES2 = [(7, 9), (16, 16), (2, 2), (5, 1), (3, 130)]
-
-
-def _disp(rng, nn, sp, dtype):
-    """Displacements that exercise clamp (far out of range), the negative floor rule, and
-    exact-integer positions."""
-    u = rnd(rng, (nn, len(sp)) + sp, dtype, 1.7)
-    flat = u.reshape(-1)
-    flat[::11] *= 9.0          # far outside
-    flat[::7] = np.round(flat[::7])  # exact integers (weights exactly 0/1)
-    flat[::13] = -np.abs(flat[::13]) - 0.25
-    return u
-
-
 @pytest.mark.parametrize("dtype", DTYPES)
 @pytest.mark.parametrize("sp", SHAPES3 + SHAPES2)
 @pytest.mark.parametrize("nn,nc,bc", [(2, 1, False), (3, 3, True), (1, 4, False)])
 def test_interp_forward_bit_exact(ext, dtype, sp, nn, nc, bc):
     rng = np.random.default_rng(hash((sp, nn, nc)) % 2**31)
     I = rnd(rng, ((1 if bc else nn), nc) + sp, dtype)
-    u = _disp(rng, nn, sp, dtype)
+    u = displacement(rng, nn, sp, dtype)
     for dt in (1.0, -0.37):
         assert_bits(ext.interp_forward(dev(I), dev(u), dt), orc.interp_forward(I, u, dt), f"interp_forward dt={dt}")
 
@@ -104,7 +52,7 @@ def test_interp_forward_bit_exact(ext, dtype, sp, nn, nc, bc):
 def test_interp_backward(ext, dtype, mode, sp, nn, nc, bc):
     rng = np.random.default_rng(hash((sp, nn, nc, 1)) % 2**31)
     I = rnd(rng, ((1 if bc else nn), nc) + sp, dtype)
-    u = _disp(rng, nn, sp, dtype)
+    u = displacement(rng, nn, sp, dtype)
     go = rnd(rng, (nn, nc) + sp, dtype)
     ext.set_splat_mode(mode)
     try:
@@ -134,7 +82,7 @@ def test_interp_backward_2d_lds_splat(ext, dtype, sp, nn, nc, bc, kind):
         u = gaussian_filter(rng.standard_normal((nn, 2) + sp), sigma=(0, 0, 6, 6), mode="wrap")
         u = (u * (3.0 / np.abs(u).max())).astype(I.dtype)
     else:
-        u = _disp(rng, nn, sp, dtype)
+        u = displacement(rng, nn, sp, dtype)
     go = rnd(rng, (nn, nc) + sp, dtype)
     for dt in (0.8, -1.0):
         for need_I, need_u in ((True, True), (True, False)):
@@ -176,7 +124,7 @@ def test_tiled_splat_any_tile_config(ext, dtype, tile):
     rng = np.random.default_rng(5)
     sp = (12, 10, 40)
     I = rnd(rng, (2, 2) + sp, dtype)
-    u = _disp(rng, 2, sp, dtype)
+    u = displacement(rng, 2, sp, dtype)
     go = rnd(rng, (2, 2) + sp, dtype)
     oI, ou = orc.interp_backward(go, I, u, 1.0, True, True)
     # shear 0: the sheared-window kernel would take every float32 3D call before the tiled kernel sees it
@@ -217,7 +165,7 @@ def test_index_math_bit_exact(ext, dtype):
 def test_interp_hessian_diagonal(ext, dtype):
     rng = np.random.default_rng(11)
     I = rnd(rng, (2, 3, 9, 8), dtype)
-    u = _disp(rng, 2, (9, 8), dtype)
+    u = displacement(rng, 2, (9, 8), dtype)
     assert_close(ext.interp_hessian_diagonal_image(dev(I), dev(u), 0.6), orc.interp_hessian_diagonal_image(I, u, 0.6),
                  dtype, "hessian diagonal")
 
@@ -434,7 +382,7 @@ def test_fused_compose_bit_exact(ext, dtype, sp):
     """ds*u + dt*interp(v, u, ds) in one kernel == the unfused expression (three roundings kept)."""
     rng = np.random.default_rng(hash(sp) % 2**31)
     d = len(sp)
-    u = _disp(rng, 2, sp, dtype)
+    u = displacement(rng, 2, sp, dtype)
     v = rnd(rng, (2, d) + sp, dtype)
     for ds, dt in ((1.0, 1.0), (-0.1, 1.0), (0.7, -1.3)):
         k = u.dtype.type
@@ -578,7 +526,7 @@ def test_vector_and_scalar_kernels_agree_bitwise(ext, dtype, sp):
     rng = np.random.default_rng(77)
     k = np.float32 if dtype == torch.float32 else np.float64
     I1, I3 = rnd(rng, (2, 1) + sp, dtype), rnd(rng, (2, 3) + sp, dtype)
-    u = _disp(rng, 2, sp, dtype)
+    u = displacement(rng, 2, sp, dtype)
     v = rnd(rng, (2, 3) + sp, dtype)
     calls = {}   # name -> (call, oracle outputs)
     for dt in (1.0, 0.9):   # both UNIT instantiations
@@ -763,7 +711,7 @@ def test_launch_order_does_not_change_results(ext):
 
     rng = np.random.default_rng(8)
     sp = (24, 20, 64)
-    phi = _disp(rng, 3, sp, torch.float32)
+    phi = displacement(rng, 3, sp, torch.float32)
     m = rnd(rng, (3, 3) + sp, torch.float32)
     go = rnd(rng, (3, 3) + sp, torch.float32)
     met = lm.FluidMetric([0.1, 0.05, 0.01])
@@ -1074,7 +1022,7 @@ def test_fused_ad_star_bit_exact(ext, dtype, sp):
     (unrolled and scalar kernels)."""
     rng = np.random.default_rng(hash(sp) % 2**31)
     d = len(sp)
-    phi = _disp(rng, 2, sp, dtype)
+    phi = displacement(rng, 2, sp, dtype)
     m = rnd(rng, (2, d) + sp, dtype)
     want = orc.jacobian_times_vectorfield_forward(phi, orc.interp_forward(m, phi, 1.0), True, False)
     pd, md = dev(phi), dev(m)
@@ -1216,7 +1164,7 @@ def test_interp_backward_fused_start_values(ext, dtype, sp, dt):
     reference operator bit for bit; otherwise it equals `start + d_u` to rounding (one summation order differs)."""
     rng = np.random.default_rng(hash((sp, dt)) % 2**31)
     d = len(sp)
-    u = _disp(rng, 2, sp, dtype)
+    u = displacement(rng, 2, sp, dtype)
     for nc, bc in ((d, False), (1, False), (2, True)):
         I = rnd(rng, (1 if bc else 2, nc) + sp, dtype)
         go = rnd(rng, (2, nc) + sp, dtype)
@@ -1247,7 +1195,7 @@ def test_ad_star_saves_the_resampled_momentum(ext, dtype, sp):
     """Ad_star(save_resampled=True) also returns interp_forward(m, phiinv), bit for bit, and the same product."""
     rng = np.random.default_rng(hash(sp) % 2**31)
     d = len(sp)
-    phi = _disp(rng, 2, sp, dtype)
+    phi = displacement(rng, 2, sp, dtype)
     m = rnd(rng, (2, d) + sp, dtype)
     for vec in (1, 0):
         ext.set_vector_kernels(vec)
@@ -1268,7 +1216,7 @@ def test_ad_star_row_tile_kernel(ext, dtype, sp):
     kernel: ragged last tiles in x and y, rows of 2 ... 250 voxels (1 to 4 z chunks), clamped faces on every side,
     far-out-of-range displacements, with and without the saved resampled momentum."""
     rng = np.random.default_rng(hash(sp) % 2**31)
-    phi = _disp(rng, 3, sp, dtype)
+    phi = displacement(rng, 3, sp, dtype)
     m = rnd(rng, (3, 3) + sp, dtype)
     want_m = orc.interp_forward(m, phi, 1.0)
     want = orc.jacobian_times_vectorfield_forward(phi, want_m, True, False)

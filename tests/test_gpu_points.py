@@ -5,6 +5,8 @@ cell for the scattered d_F (tests/scatter_bound.py), and through torch.autograd.
 Shapes: (5, 6, 7), (7, 9) and (8, 16, 32) are general; (1, 5, 4), (6, 1, 3) and (1, 9) have one-voxel extents and a thin
 z (nz == 1: Lerp3's single loads); in (2, 2, 2) a corner pair is the whole row.  Point counts: 1 is a single lane, 63, 64
 and 65 sit around a wave, 257 crosses a workgroup, 1000 gives several blocks with a tail."""
+import functools
+
 import numpy as np
 import pytest
 import torch
@@ -12,29 +14,20 @@ import torch
 import labels_ref
 import points_ref as ref
 import scatter_bound
+from gpu_util import assert_close, dev
 
 pytestmark = pytest.mark.gpu
 
 N = 2
 SHAPES = ref.SHAPES
 PS = ref.POINT_COUNTS
-RTOL = {np.dtype(np.float32): 1e-5, np.dtype(np.float64): 1e-12}   # the project's parity criterion: rtol * max |reference|
+_close = functools.partial(assert_close, floor=0, record=False)   # the bound is RTOL * max|want| exactly: no floor under a zero reference
 both_dtypes = pytest.mark.parametrize("dtype", [np.float32, np.float64], ids=["f32", "f64"])
 all_shapes = pytest.mark.parametrize("sp", SHAPES, ids=str)
 
 
-def _dev(x):
-    return torch.from_numpy(np.ascontiguousarray(x)).cuda()
-
-
 def _channels(sp):
     return sorted({1, len(sp), 4})
-
-
-def _close(got, want, dtype, what):
-    got = got.detach().cpu().numpy().astype(np.float64)
-    err, tol = np.abs(got - want).max(), RTOL[np.dtype(dtype)] * np.abs(want).max()
-    assert err <= tol, f"{what}: max error {err:.3e} over {tol:.3e}"
 
 
 def _same_bits(a, b):
@@ -61,11 +54,11 @@ def test_same_bits_as_interp(sp, dtype):
         if kind in ("random", "normal"):
             out = ref.outside(p, sp)
             assert out.mean() > 0.02 and (min(sp) < 5 or not out.all()), kind   # some samples leave the grid, some stay
-        ud, pd = _dev(u), _dev(p)
+        ud, pd = dev(u), dev(p)
         for C in _channels(sp):
             I = ref.field(N, C, sp, dtype)
             for bc in (False, True):
-                Id = _dev(I[:1] if bc else I)
+                Id = dev(I[:1] if bc else I)
                 got = lm.interp_points(Id, pd)
                 want = lm.interp(Id, ud).reshape(N, C, -1)
                 assert got.shape == (N, C, int(np.prod(sp))) and got.dtype == Id.dtype
@@ -89,15 +82,15 @@ def test_scattered_positions_against_the_reference(sp, dtype):
         x, first = ref.scattered(N, sp, P, dtype)
         assert ref.outside(x[:, :, first:], sp).mean() >= 0.25, P     # of the wide half, a quarter or more is outside
         assert not ref.outside(x[:, :, :first], sp).any()
-        xd = _dev(x)
+        xd = dev(x)
         for C in _channels(sp):
             F = ref.field(N, C, sp, dtype, seed=P)
             g = ref.upstream(N, C, P, dtype)
-            gd = _dev(g)
+            gd = dev(g)
             for bc in (False, True):
                 Fh = F[:1] if bc else F
                 val, grad = ref.sample(Fh, x)
-                Fd, xg = _dev(Fh), xd.clone().requires_grad_(True)
+                Fd, xg = dev(Fh), xd.clone().requires_grad_(True)
                 out = lm.interp_points(Fd, xg)
                 assert out.shape == (N, C, P)
                 _close(out, val, dtype, f"values {sp} P {P} C {C} bc {bc}")
@@ -122,12 +115,12 @@ def test_far_and_non_finite_positions(sp, dtype):
             x[:, a] = far
             xe[:, a] = edge
             assert x.dtype == np.dtype(dtype) and np.all(x[:, a].astype(np.float64) == far)
-            xg = _dev(x).requires_grad_(True)
-            out = lm.interp_points(_dev(F), xg)
+            xg = dev(x).requires_grad_(True)
+            out = lm.interp_points(dev(F), xg)
             val, grad = ref.sample(F, x)
             _close(out, val, dtype, f"far values {sp} axis {a}")
             _close(out, ref.sample(F, xe)[0], dtype, f"border values {sp} axis {a}")     # the border value
-            out.backward(_dev(g))
+            out.backward(dev(g))
             assert torch.all(xg.grad[:, a] == 0), (a, far)                             # no gradient along that axis
             _close(xg.grad, (g[:, :, None, :].astype(np.float64) * grad).sum(1), dtype, f"far d_x {sp} axis {a}")
     # coordinates that are not finite: NaN for that point, every other point untouched
@@ -135,8 +128,8 @@ def test_far_and_non_finite_positions(sp, dtype):
     bad = {0: np.nan, 7: np.inf, 64: -np.inf}
     for p, v in bad.items():
         x[:, p % d, p] = v
-    out = lm.interp_points(_dev(F), _dev(x)).cpu().numpy()
-    want = lm.interp_points(_dev(F), _dev(base)).cpu().numpy()
+    out = lm.interp_points(dev(F), dev(x)).cpu().numpy()
+    want = lm.interp_points(dev(F), dev(base)).cpu().numpy()
     for p in range(P):
         if p in bad:
             assert np.all(np.isnan(out[:, :, p])), p
@@ -172,18 +165,18 @@ def test_d_F_cell_by_cell(sp, dtype):
         wide = ref.scatter_wide(g, x, sp, NF)
         if kind == "crowd":      # many atomics on few cells: every contribution lands on the 2^d corners of one cell
             assert (wide[2][0, 0] > 0).sum() <= 2 ** len(sp) and wide[2].max() >= P
-        Fd, xd, gd = _dev(F).requires_grad_(True), _dev(x).requires_grad_(True), _dev(g)
+        Fd, xd, gd = dev(F).requires_grad_(True), dev(x).requires_grad_(True), dev(g)
         lm.interp_points(Fd, xd).backward(gd)
         assert Fd.grad.shape == Fd.shape
         what = f"d_F {sp} {np.dtype(dtype).name} {kind} P {P} C {C} bc {bc}"
         worst = max(worst, scatter_bound.assert_cells(Fd.grad.cpu().numpy(), wide, dtype, what))
-        assert torch.all(Fd.grad[_dev(wide[2] == 0)] == 0)          # cells that receive nothing: exactly 0
+        assert torch.all(Fd.grad[dev(wide[2] == 0)] == 0)          # cells that receive nothing: exactly 0
         # need_F without need_x and the reverse: the gradient that was not requested is None
-        F2, x2 = _dev(F).requires_grad_(True), _dev(x)
+        F2, x2 = dev(F).requires_grad_(True), dev(x)
         lm.interp_points(F2, x2).backward(gd)
         assert x2.grad is None
         worst = max(worst, scatter_bound.assert_cells(F2.grad.cpu().numpy(), wide, dtype, what + " (need_F only)"))
-        F3, x3 = _dev(F), _dev(x).requires_grad_(True)
+        F3, x3 = dev(F), dev(x).requires_grad_(True)
         lm.interp_points(F3, x3).backward(gd)
         assert F3.grad is None and torch.equal(x3.grad, xd.grad)
         d_F, d_x = ext.interp_points_backward(gd, F3, x2, True, False)
@@ -202,9 +195,9 @@ def test_gradcheck(sp, bc):
     import lagomorph_amd as lm
 
     d, P = len(sp), 9
-    x = _dev(ref.interior(N, sp, P, np.float64)).requires_grad_(True)       # fractions in [0.1, 0.9]: eps crosses no face
-    F = _dev(ref.field(1 if bc else N, 3, sp, np.float64)).requires_grad_(True)
-    u = _dev(0.5 * ref.field(1 if bc else N, d, sp, np.float64, seed=2)).requires_grad_(True)
+    x = dev(ref.interior(N, sp, P, np.float64)).requires_grad_(True)       # fractions in [0.1, 0.9]: eps crosses no face
+    F = dev(ref.field(1 if bc else N, 3, sp, np.float64)).requires_grad_(True)
+    u = dev(0.5 * ref.field(1 if bc else N, d, sp, np.float64, seed=2)).requires_grad_(True)
     # (nondet_tol: d_F is a sum of float atomics, its last bits differ between the two backward runs gradcheck compares)
     kw = dict(eps=1e-5, atol=1e-8, rtol=1e-6, nondet_tol=1e-10)
     assert torch.autograd.gradcheck(lm.interp_points, (F, x), **kw)
@@ -223,7 +216,7 @@ def test_deform_points(sp, dtype):
     d, P = len(sp), 257
     u = labels_ref.displacement("random", N, sp, dtype)
     x, _ = ref.scattered(N, sp, P, dtype, seed=2)
-    ud, xd = _dev(u), _dev(x)
+    ud, xd = dev(u), dev(x)
     for bc in (False, True):
         uu = ud[:1].contiguous() if bc else ud
         for dt in (1.0, -0.5):
@@ -231,7 +224,7 @@ def test_deform_points(sp, dtype):
             assert got.shape == (N, d, P) and torch.equal(got, xd + dt * lm.interp_points(uu, xd)), (bc, dt)
         assert torch.equal(lm.deform_points(xd, uu), lm.deform_points(xd, uu, 1.0))
     # the identity grid as the point set: identity + u exactly, which is also identity + compose(0 u, u)
-    ident = _dev(lm.identity((N, d) + sp, dtype=dtype))
+    ident = dev(lm.identity((N, d) + sp, dtype=dtype))
     got = lm.deform_points(ident.reshape(N, d, -1), ud).reshape((N, d) + sp)
     assert torch.equal(got, ident + ud)
     assert torch.equal(got, ident + lm.compose(0 * ud, ud))
@@ -243,7 +236,7 @@ def test_deform_points(sp, dtype):
     for a, n in enumerate(sp):
         lo, hi = max(0.0, -shift[a]), min(n - 1.0, n - 1.0 - shift[a])
         lms[:, a] = lo + rng.integers(0, int(8 * (hi - lo)) + 1, (N, 40)) / 8.0
-    lmd = _dev(lms.astype(dtype))
+    lmd = dev(lms.astype(dtype))
     t = torch.tensor(shift, dtype=lmd.dtype, device="cuda").view(1, d, 1)
     const = (t.view((1, d) + (1,) * d) * torch.ones((1, d) + sp, dtype=lmd.dtype, device="cuda")).contiguous()
     tre = lm.landmark_distance(lm.deform_points(lmd, const), lmd + t, spacing=(0.8, 1.0, 1.5)[:d])

@@ -23,9 +23,10 @@ import torch
 
 import affine_box_cases as abc
 import scatter_cases as sc
+from gpu_util import DTYPES, OBSERVED, SHAPES2, SHAPES3, dev, host
 from oracle import lago_oracle as orc
-from scatter_bound import assert_cells, maxnorm_units, worst_ratio
-from test_gpu_parity import DTYPES, OBSERVED, RTOL, SHAPES2, SHAPES3, dev, host
+from parity_rule import rtol, units
+from scatter_bound import assert_cells, worst_ratio
 
 pytestmark = pytest.mark.gpu
 
@@ -91,14 +92,14 @@ def judge(got, wide, dtype, op, path, what, start=None, ref=None):
     comparison HIP against oracle under 'direct <op> [<path>]' -- so that profiles/scatter_cell_bound.md can say how much
     of a direct figure is the oracle's own summation error."""
     g = host(got) if torch.is_tensor(got) else np.asarray(got)
-    t, rtol = tag(dtype), RTOL[dtype]
+    t = tag(dtype)
     _note(f"cell {op} [{path}] {t}", worst_ratio(g, wide, npdt(dtype), start))
     if start is None:
-        _note(f"wide {op} [{path}] {t}", maxnorm_units(g, wide[0], rtol))
+        _note(f"wide {op} [{path}] {t}", units(g, wide[0], dtype))
         if ref is not None:
             _note(f"cell {op} [oracle] {t}", worst_ratio(ref, wide, npdt(dtype)))
-            _note(f"wide {op} [oracle] {t}", maxnorm_units(ref, wide[0], rtol))
-            _note(f"direct {op} [{path}] {t}", maxnorm_units(g, ref, rtol))
+            _note(f"wide {op} [oracle] {t}", units(ref, wide[0], dtype))
+            _note(f"direct {op} [{path}] {t}", units(g, ref, dtype))
     return assert_cells(g, wide, npdt(dtype), f"{what} [{path}]", start, ref)
 
 
@@ -498,14 +499,13 @@ def _affine_parameter_gradients(ext, dtype, go, I, A, T, what):
     _, dA, dT = ext.affine_interp_backward(dev(go), dev(I), dev(A), dev(T), False, True, True)
     _, oA, oT = orc.affine_interp_backward(go, I, A, T, False, True, True)
     _, wA, wT = orc.affine_interp_backward_wide(go, I, A, T, False, True, True)
-    rtol = RTOL[dtype]
     for name, got, ref, w in (("d_A", host(dA), oA, wA), ("d_T", host(dT), oT, wT)):
-        hip_units, orc_units = maxnorm_units(got, w[0], rtol), maxnorm_units(ref, w[0], rtol)
+        hip_units, orc_units = units(got, w[0], dtype), units(ref, w[0], dtype)
         for who, val in (("HIP", hip_units), ("oracle", orc_units)):
             key = f"wide affine {name} [{who}] {tag(dtype)}"
             OBSERVED[key] = max(OBSERVED.get(key, 0.0), val)
-        print(f"{what} {name}: HIP {hip_units:.4f}, oracle {orc_units:.4f} of {rtol:.0e} x max |wide sum|")
-        assert hip_units <= 1.0, f"{what} {name}: HIP is {hip_units:.3f} x {rtol:.0e} x max from the wide sum (oracle: {orc_units:.3f})"
+        print(f"{what} {name}: HIP {hip_units:.4f}, oracle {orc_units:.4f} of {rtol(dtype):.0e} x max |wide sum|")
+        assert hip_units <= 1.0, f"{what} {name}: HIP is {hip_units:.3f} x {rtol(dtype):.0e} x max from the wide sum (oracle: {orc_units:.3f})"
 
 
 @pytest.mark.parametrize("dtype", DTYPES)

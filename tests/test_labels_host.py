@@ -9,9 +9,7 @@
   sizing of label_overlap's scratch."""
 import ctypes
 import os
-import shutil
 import struct
-import subprocess
 from fractions import Fraction
 
 import numpy as np
@@ -19,9 +17,9 @@ import pytest
 import torch
 
 import labels_ref as ref
+import native_build
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-CXX = next((c for c in ("c++", "g++", "clang++") if shutil.which(c)), None)
 SHAPES = ((5, 6, 7), (7, 9), (8, 16, 32), (1, 5, 4), (6, 1, 3), (2, 2, 2), (1, 9))
 
 
@@ -124,11 +122,7 @@ def test_vote_is_the_argmax_of_a_trilinear_one_hot(sp):
 # ---- the header against the reference
 
 def _build_emul(tmp_path, name, extra=()):
-    exe = str(tmp_path / name)
-    # -ffp-contract=off as the library itself is built (lagomorph_amd/build.py): the double expressions keep their order
-    subprocess.run([CXX, "-O2", "-std=c++17", "-ffp-contract=off", "-Wall", "-Werror", *extra, "-o", exe,
-                    os.path.join(HERE, "native", "label_emul.cpp")], check=True, timeout=600)
-    return exe
+    return native_build.build(tmp_path, "label_emul.cpp", extra=extra, name=name)
 
 
 def _emul_cases():
@@ -164,14 +158,13 @@ def _read_results(path, cases):
     assert at == len(raw)
 
 
-@pytest.mark.skipif(CXX is None, reason="no C++ compiler available")
+@native_build.needs_cxx
 def test_header_emulation_equals_the_reference_exactly(tmp_path):
     cases = list(_emul_cases())
     assert len(cases) > 1400
     src, dst = str(tmp_path / "cases.bin"), str(tmp_path / "out.bin")
     _write_cases(src, cases)
-    r = subprocess.run([_build_emul(tmp_path, "label_emul"), src, dst], capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, (r.returncode, r.stdout, r.stderr)
+    native_build.run(_build_emul(tmp_path, "label_emul"), src, dst)
     moved = ties = 0
     for (sp, dtype, NL, L, u, dt), (nearest, vote, lo, hi, t) in zip(cases, _read_results(dst, cases)):
         N, d = u.shape[0], len(sp)
@@ -191,7 +184,7 @@ def test_header_emulation_equals_the_reference_exactly(tmp_path):
     assert moved > 10000 and ties > 500   # the cases do move labels, and exact ties between two labels are among them
 
 
-@pytest.mark.skipif(CXX is None, reason="no C++ compiler available")
+@native_build.needs_cxx
 def test_header_emulation_under_the_sanitizers(tmp_path):
     """The same stand-alone host program with AddressSanitizer and UndefinedBehaviorSanitizer: the corner indices,
     conversions of out-of-range, infinite and NaN positions included, stay defined and inside the label map."""
@@ -199,8 +192,7 @@ def test_header_emulation_under_the_sanitizers(tmp_path):
     src, dst = str(tmp_path / "cases.bin"), str(tmp_path / "out.bin")
     _write_cases(src, cases)
     exe = _build_emul(tmp_path, "label_emul_san", ("-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"))
-    r = subprocess.run([exe, src, dst], capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0 and not r.stderr.strip(), (r.returncode, r.stdout, r.stderr[-2000:])
+    native_build.run(exe, src, dst, quiet=True)
     for (sp, dtype, NL, L, u, dt), (nearest, vote, lo, hi, t) in zip(cases, _read_results(dst, cases)):
         assert np.array_equal(vote.reshape((u.shape[0], 1) + sp), ref.warp(L, u, dt, "vote"))
 

@@ -6,24 +6,15 @@ selects a wrong instantiation silently.  tests/native/launch_dispatch_emul.cpp i
 compiler and checks, for 1 to 4 flags over every runtime combination, alone and nested inside with_dim and
 with_int<256, 512, 1024>: the compile-time values received equal the runtime values passed, position by position; f is
 called exactly once per dispatch; with_int returns false without calling f for a value outside its list."""
-import os
 import re
-import shutil
-import subprocess
 
-import pytest
+import native_build
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-CXX = next((c for c in ("c++", "g++", "clang++", "hipcc") if shutil.which(c)), None)
-pytestmark = pytest.mark.skipif(CXX is None, reason="no C++ compiler available")
+pytestmark = native_build.needs_cxx_or_hipcc
 
 
 def test_dispatch_values_positions_and_single_call(tmp_path):
-    exe = str(tmp_path / "launch_dispatch_emul")
-    src = os.path.join(HERE, "native", "launch_dispatch_emul.cpp")
-    lang = ["-x", "c++"] if CXX == "hipcc" else []   # (as host code only: the dispatch part needs no HIP)
-    subprocess.run([CXX, "-O1", "-std=c++17", "-Wall", "-Werror", *lang, "-o", exe, src], check=True, timeout=600)
-    r = subprocess.run([exe], capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, r.stdout + r.stderr
+    # (as host code only: the dispatch part needs no HIP)
+    r = native_build.run(native_build.build(tmp_path, "launch_dispatch_emul.cpp", "-O1", fp_contract_off=False, compiler=native_build.CXX_OR_HIPCC))
     m = re.search(r"(\d+) checks, 0 failed", r.stdout)
     assert m and int(m.group(1)) > 500, r.stdout

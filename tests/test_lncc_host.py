@@ -10,6 +10,7 @@ import pytest
 import torch
 
 import lncc_ref
+import parity_rule
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 MODES = lncc_ref.MODES
@@ -68,7 +69,7 @@ def test_float32_emulation_of_the_shared_cases_is_within_half_the_gpu_tolerance(
             for mode in MODES:
                 em = lncc_ref.emulate(np.float32)(*lncc_ref.inputs(sp, kind), sigma, mode=mode)
                 ref = lncc_ref.reference(sp, kind, sigma, mode)
-                u = [lncc_ref.units(a, b, np.float32) for a, b in zip(em, ref)]
+                u = [parity_rule.units(a, b, np.float32) for a, b in zip(em, ref)]
                 worst = max(worst, max(u))
                 assert max(u) <= 0.5, f"{sp} {kind} sigma={sigma} {mode}: cc, dI, dJ at {u} of the tolerance"
     print(f"{sp}: worst {worst:.3f} of the tolerance")

@@ -7,19 +7,14 @@
   through its functions with a plain host compiler, and the table equals mi_ref's integer for integer (indices, window
   derivatives and the backward sums bit for bit as well);
 - the Python layer's argument errors, and the shim's refusal of CPU tensors."""
-import os
-import shutil
 import struct
-import subprocess
 
 import numpy as np
 import pytest
 import torch
 
 import mi_ref
-
-HERE = os.path.dirname(os.path.abspath(__file__))
-CXX = next((c for c in ("c++", "g++", "clang++") if shutil.which(c)), None)
+import native_build
 
 
 # ---- the reference against itself
@@ -78,11 +73,7 @@ def test_reference_gradient_against_central_differences(B, normalized):
 # ---- the header against the reference
 
 def _emul(tmp_path):
-    exe = str(tmp_path / "mi_emul")
-    # -ffp-contract=off as the library itself is built (lagomorph_amd/build.py): the double expressions keep their order
-    subprocess.run([CXX, "-O2", "-std=c++17", "-ffp-contract=off", "-Wall", "-o", exe,
-                    os.path.join(HERE, "native", "mi_emul.cpp")], check=True, timeout=600)
-    return exe
+    return native_build.build(tmp_path, "mi_emul.cpp", werror=False)
 
 
 def _run_emul(exe, tmp_path, B, rI, rJ, I, J, G):
@@ -92,8 +83,7 @@ def _run_emul(exe, tmp_path, B, rI, rJ, I, J, G):
         f.write(struct.pack("<ii4d", B, n, rI[0], rI[1], rJ[0], rJ[1]))
         for a in (I, J, G):
             f.write(np.ascontiguousarray(a, dtype="<f8").tobytes())
-    r = subprocess.run([exe, src, dst], capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, (r.returncode, r.stdout, r.stderr)
+    native_build.run(exe, src, dst)
     raw = open(dst, "rb").read()
     out, at = [], 0
     for dt, cnt in (("<i8", B * B), ("<i4", n), ("<i4", n), ("<f8", 4 * n), ("<f8", 4 * n), ("<f8", n), ("<f8", n)):
@@ -107,7 +97,7 @@ def _bits(a):
     return np.ascontiguousarray(a, dtype=np.float64).view(np.uint64)
 
 
-@pytest.mark.skipif(CXX is None, reason="no C++ compiler available")
+@native_build.needs_cxx
 def test_header_emulation_equals_the_reference_integer_for_integer(tmp_path):
     """B in {4, 5, 32, 64}; noise voxels of float32 and of full float64 values, values exactly lo and hi, values outside
     the range, NaN, +inf and -inf in either image."""

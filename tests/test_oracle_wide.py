@@ -13,22 +13,22 @@ import numpy as np
 import pytest
 
 import affine_box_cases as abc
+import parity_rule
 import scatter_cases as sc
 from oracle import lago_oracle as orc
-from scatter_bound import assert_cells, cell_bound, maxnorm_units, violations, worst_ratio
+from scatter_bound import assert_cells, cell_bound, violations, worst_ratio
 
-SHAPES3 = [(5, 6, 7), (8, 8, 8), (3, 4, 1), (2, 2, 2), (9, 5, 70), (6, 5, 16), (3, 4, 128)]   # test_gpu_parity.SHAPES3
-SHAPES2 = [(7, 9), (16, 16), (2, 2), (5, 1), (3, 130)]                                          # test_gpu_parity.SHAPES2
+SHAPES3 = [(5, 6, 7), (8, 8, 8), (3, 4, 1), (2, 2, 2), (9, 5, 70), (6, 5, 16), (3, 4, 128)]   # gpu_util.SHAPES3
+SHAPES2 = [(7, 9), (16, 16), (2, 2), (5, 1), (3, 130)]                                          # gpu_util.SHAPES2  
 NPDT = [np.float32, np.float64]
-RTOL = {np.float32: 1e-5, np.float64: 1e-12}
 
 
 def test_shape_lists_are_those_of_the_parity_suite():
-    """The shape lists above are copies (importing tests/test_gpu_parity.py would pull torch into this module)."""
+    """The shape lists above are copies (importing tests/gpu_util.py would pull torch into this module)."""
     import ast
     import os
 
-    tree = ast.parse(open(os.path.join(os.path.dirname(__file__), "test_gpu_parity.py")).read())
+    tree = ast.parse(open(os.path.join(os.path.dirname(__file__), "gpu_util.py")).read())
     got = {t.id: ast.literal_eval(n.value) for n in tree.body if isinstance(n, ast.Assign)
            for t in n.targets if isinstance(t, ast.Name) and t.id in ("SHAPES3", "SHAPES2")}
     assert got == {"SHAPES3": SHAPES3, "SHAPES2": SHAPES2}
@@ -260,12 +260,12 @@ def test_seeded_defects_pass_the_max_norm_and_fail_the_bound(sp):
     # the control: the numpy splat without a defect is the oracle's operator -- inside the bound, and accepted before
     good = _numpy_splat(go, u)
     assert_cells(good, wide, npdt, f"numpy splat without defect {sp}")
-    assert maxnorm_units(good, oI, 1e-5) <= 1.0
+    assert parity_rule.units(good, oI, np.float32) <= 1.0
     old_bound = 1e-5 * float(np.abs(oI).max())
     cases = {"drop": _numpy_splat(go, u, defect="drop"), "fraction": _numpy_splat(go, u, defect="fraction"),
              "lost corner": _numpy_splat(go, u, lose=_quiet_contribution(go, u, wide, old_bound))}
     for name, bad in cases.items():
-        units = maxnorm_units(bad, oI, 1e-5)
+        units = parity_rule.units(bad, oI, np.float32)
         cells = int(violations(bad, wide, npdt).sum())
         print(f"{sp} {name}: {units:.4f} of the max-norm bound, {cells} cells over the cell-wise bound, "
               f"worst {worst_ratio(bad, wide, npdt):.1f} x")
@@ -286,8 +286,8 @@ def test_weight_defects_show_on_the_suite_data_too(sp):
     for defect in ("drop", "fraction"):
         bad = _numpy_splat(go, u, defect=defect)
         cells = int(violations(bad, wide, np.float32).sum())
-        print(f"{sp} {defect}, unplanted: {maxnorm_units(bad, oI, 1e-5):.4f} of the max-norm bound, {cells} cells over")
-        assert maxnorm_units(bad, oI, 1e-5) <= 1.0
+        print(f"{sp} {defect}, unplanted: {parity_rule.units(bad, oI, np.float32):.4f} of the max-norm bound, {cells} cells over")
+        assert parity_rule.units(bad, oI, np.float32) <= 1.0
         assert cells >= 1
 
 
@@ -359,4 +359,4 @@ def test_upcast_float64_oracle_is_not_a_yardstick():
     assert violations(o32, upcast, np.float32).any()
     assert worst_ratio(o32, upcast, np.float32) > 100.0
     # while the two agree in the max norm: the difference is invisible to the older criterion
-    assert maxnorm_units(o32, o64, 1e-5) <= 1.0
+    assert parity_rule.units(o32, o64, np.float32) <= 1.0
