@@ -69,6 +69,10 @@ extern "C" {
 #define LAGO_ENERGY_DIFFUSION 0
 #define LAGO_ENERGY_BENDING 1
 
+/* lago_pyramid_down, lago_pyramid_up: which per-axis matrix (down applies R or E^T, up applies E or R^T) */
+#define LAGO_PYRAMID_REDUCE 0
+#define LAGO_PYRAMID_EXPAND 1
+
 /* ---- housekeeping --------------------------------------------------------- */
 
 /* replaces set_debug_mode (extension.cpp:105-107): when non-zero every entry
@@ -549,7 +553,38 @@ long long lago_reversed_launches(void);
      * (no scratch), and out overlapping u or scale.  Empty problems: nothing is done (LAGO_OK). */                  \
     int lago_field_energy_operator##SUF(REAL *out, const REAL *u, const REAL *scale, int kind, int dim, int64_t nn,   \
                                         int64_t nc, int64_t nx, int64_t ny, int64_t nz, const double *spacing,        \
-                                        void *stream);
+                                        void *stream);                                                               \
+    /* lago_pyramid_down: one level of an image pyramid, from the fine grid to the coarse one.  in: (rows, nx, ny    \
+     * [, nz]), the FINE field, rows = batch items times channels; out: (rows, mx, my[, mz]).  Per axis with fine     \
+     * extent n the coarse extent is m = (n + 1) / 2 and coarse voxel j sits at fine voxel 2 j; the extents passed   \
+     * are always the fine grid's (dim 2: nz is ignored).  out = scale (Mx (x) My (x) Mz) in with, per axis, op =    \
+     *   LAGO_PYRAMID_REDUCE  M = R (m x n), (R a)[j] = sum_{k=-2..2} w_k a[clamp(2 j + k, 0, n - 1)],               \
+     *                        w = (1, 4, 6, 4, 1) / 16: the anti-aliased reduce, rows sum to 1;                      \
+     *   LAGO_PYRAMID_EXPAND  M = E^T, the exact transpose of the expand of lago_pyramid_up (its backward).          \
+     * Workgroups own fine tiles of 8 x 8 x 64 (dim 2: 64 x 64) staged in LDS with a halo of two voxels and contract \
+     * the axes one after the other in LDS, the contiguous axis first (z, y, x), five taps ascending, each a product \
+     * and an addition (csrc/pyramid_weights.hpp: no fma), then the scale: at most 5 dim + 1 roundings per element.  \
+     * 4 bytes loaded per fine element and 4 stored per coarse one (float32); every element has one owner, no        \
+     * atomics, no scratch: the same bits from call to call, and exact results for integer-valued inputs up to 512   \
+     * in magnitude.  Nothing is allocated and nothing synchronises.  LAGO_ERR_INVALID before any device call: dim   \
+     * not 2 or 3, a negative extent, a plane of 2^29 elements or more, an unknown op, a null pointer, out           \
+     * overlapping in.  rows or an extent equal to 0: nothing is done (LAGO_OK).  No counterpart in the reference. */ \
+    int lago_pyramid_down##SUF(REAL *out, const REAL *in, int op, int dim, int64_t rows, int64_t nx, int64_t ny,     \
+                               int64_t nz, double scale, void *stream);                                              \
+    /* lago_pyramid_up: from the coarse grid to the fine one.  in: (rows, mx, my[, mz]); out: (rows, nx, ny[, nz]),  \
+     * the FINE field, whose extents are the ones passed (both n = 2 m and n = 2 m - 1 belong to a coarse extent m). \
+     * out = scale (Mx (x) My (x) Mz) in with, per axis, op =                                                        \
+     *   LAGO_PYRAMID_EXPAND  M = E (n x m), (E c)[2 j] = c[j], (E c)[2 j + 1] = (c[j] + c[min(j + 1, m - 1)]) / 2:   \
+     *                        linear prolongation, rows sum to 1 (scale = 2 carries a displacement in voxel units    \
+     *                        to the finer grid);                                                                    \
+     *   LAGO_PYRAMID_REDUCE  M = R^T, the exact transpose of the reduce (its backward; 2 R^T is NOT E: it does not  \
+     *                        preserve constants at the border).                                                     \
+     * Workgroups own fine tiles of 8 x 8 x 64 (dim 2: 64 x 64), stage the 6 x 6 x 34 coarse voxels a tile reaches   \
+     * in LDS and contract x, then y, then z, three taps ascending, each a product and an addition, then the scale.  \
+     * 4 bytes stored per fine element (float32), an eighth of that loaded; one owner per element, no atomics: the   \
+     * same bits from call to call.  Errors and empty problems as lago_pyramid_down. */                              \
+    int lago_pyramid_up##SUF(REAL *out, const REAL *in, int op, int dim, int64_t rows, int64_t nx, int64_t ny,       \
+                             int64_t nz, double scale, void *stream);
 
 LAGO_DECLARE(float, _f32)
 LAGO_DECLARE(double, _f64)

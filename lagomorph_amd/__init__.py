@@ -28,6 +28,8 @@ if not _BUILDING:
     from .lddmm import EPDiff_step, LDDMMAtlasBuilder, expmap, expmap_advect, lddmm_step, shard_indices  # noqa: F401
     from .metric import FluidMetric, FluidMetricOperator, GaussianMetric, Metric  # noqa: F401
     from .points import InterpPointsFunction, deform_points, interp_points, landmark_distance  # noqa: F401
+    from .pyramid import (PyramidFunction, image_pyramid, pyramid_expand, pyramid_expand_adjoint,  # noqa: F401
+                          pyramid_reduce, pyramid_restrict_adjoint, pyramid_shape)
     from .regularize import (EnergyOperatorFunction, FieldEnergyFunction, bending_energy, diffusion_energy,  # noqa: F401
                              energy_operator, field_energy)
     from .similarity import (JointHistogramFunction, LNCCFunction, LNCCSimilarity, MISimilarity,  # noqa: F401

@@ -91,6 +91,8 @@ _SIGS = {
     "lago_ffd_expand_adjoint": [_vp, _vp, _vp, _i64, _int, _i64, _i64, _i64, _i64, _int, _int, _int, _vp],
     "lago_field_energy": [_vp, _vp, _vp, _i64, _int, _int, _i64, _i64, _i64, _i64, _i64, ctypes.POINTER(_dbl), _vp],
     "lago_field_energy_operator": [_vp, _vp, _vp, _int, _int, _i64, _i64, _i64, _i64, _i64, ctypes.POINTER(_dbl), _vp],
+    "lago_pyramid_down": [_vp, _vp, _int, _int, _i64, _i64, _i64, _i64, _dbl, _vp],
+    "lago_pyramid_up": [_vp, _vp, _int, _int, _i64, _i64, _i64, _i64, _dbl, _vp],
     "lago_fluid_metric": [_vp, _vp, _vp, _i64, _int, _vp, _vp, _vp, _vp, _vp, _vp, _dbl, _dbl, _dbl, _int, _i64, _i64,
                           _i64, _i64, _vp],
     "lago_fluid_metric_scaled": [_vp, _vp, _vp, _i64, _int, _vp, _vp, _vp, _vp, _vp, _vp, _dbl, _dbl, _dbl, _int, _i64,
